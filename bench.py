@@ -9,13 +9,16 @@ axis=0)` (mdir/components/optim/score/cirscore.py:69-70).  Inputs are resident i
 HBM when the timed region starts.  With --gpus N the 1M database is row-sharded
 (strong scaling); see mdir_amd/sharded.py for the exchange.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows ROWS] [--no-cpu-baseline] [--secondary]
-                    [--extract-images M] [--profile] [--comm torch|mdx|p2p]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows ROWS] [--full] [--dump-outputs DIR] [--no-cpu-baseline]
+                    [--secondary] [--extract-images M] [--profile] [--comm torch|mdx|p2p]
 
-The default run = the headline loop + `cpu_baseline` (with the float64 arbiter of `cpu_path_parity`) + the descriptors/s leg
-(with its own `cpu_baseline` and trunk `roofline`).  `--secondary` appends the side legs of tools/bench_secondary.py.
-`--profile` = the headline loop alone (no CPU baseline, side legs or extraction): the form tools/profile_round.sh runs under
-rocprofv3, so that the per-kernel averages of the committed profile add up to the step.
+The default run = what the headline figure needs: set-up, warm-up, the K timed steps, mAP-medium of the last step's ranking and
+the figures derived from the timed steps' own HIP events.  `--full` adds the device-side checks of the ranking, `cpu_baseline`
+(with the float64 arbiter of `cpu_path_parity`) and the descriptors/s leg (with its own `cpu_baseline` and trunk `roofline`).
+`--secondary` (implies `--full`) appends the side legs of tools/bench_secondary.py.  `--profile` = the headline loop alone
+(no CPU baseline, side legs or extraction): the form tools/profile_round.sh runs under rocprofv3, so that the per-kernel
+averages of the committed profile add up to the step.  `--dump-outputs DIR` writes a fixed, seeded sample of the last timed
+step's scores and ranking (`dump_outputs`), so that two builds can be compared output for output on identical inputs.
 
 Prints ONE JSON line on rank 0.
 """
@@ -201,19 +204,39 @@ def verify_ranking(sc, rk):
     return ok_perm, ok_order
 
 
+def dump_outputs(out_dir, sc, rk):
+    """`--dump-outputs`: what the timed path handed its caller in the last step -- scores ``sc`` [Q,N] fp32 and the full ranking
+    ``rk`` [Q,N] int64 -- as a fixed, seeded sample (the whole pair is ~0.8 GB at the headline size): ``scores.npy`` = the scores
+    of 65 536 sampled database rows (float32, columns in ascending id order), ``ranking.npy`` = the ids at the first 1 024
+    ranking positions and at 31 744 sampled later positions (float64: exact for any id), ~37 MB together.  The samples depend
+    on N alone, so two runs with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = sc.shape[1]
+    rng = np.random.default_rng(2048)
+    cols = np.sort(rng.choice(n, size=min(n, 65536), replace=False))
+    head = min(n, 1024)
+    pos = np.concatenate([np.arange(head), head + np.sort(rng.choice(n - head, size=min(n - head, 32768 - head), replace=False))])
+    np.save(os.path.join(out_dir, "scores.npy"), sc[:, torch.from_numpy(cols).to(sc.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "ranking.npy"), rk[:, torch.from_numpy(pos).to(rk.device)].cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", dest="n", type=int, default=N_ROXFORD + N_DISTRACTORS, help="database rows (default 1 004 993)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the ranking on the device and run the CPU baseline (with the float64 arbiter) and the descriptors/s leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's scores (float32) and ranking (float64 ids) to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--secondary", action="store_true",
-                    help="also run the side legs of tools/bench_secondary.py (configs[1] / configs[4] shapes, split-precision modes, top-100, "
-                         "one evaluation, whitening learning, CLAHE, the sort-free route) and append them to the line")
+                    help="(implies --full) also run the side legs of tools/bench_secondary.py (configs[1] / configs[4] shapes, split-precision "
+                         "modes, top-100, one evaluation, whitening learning, CLAHE, the sort-free route) and append them to the line")
     ap.add_argument("--no-secondary", action="store_true", help="(accepted for older command lines: the side legs are off by default)")
     ap.add_argument("--extract-images", type=int, default=40,
-                    help="images PER SIZE (16 sizes) of the (untimed) descriptors/sec leg: ResNet101-GeM, 3 scales + whitening; 0 = skip")
+                    help="with --full: images PER SIZE (16 sizes) of the (untimed) descriptors/sec leg: ResNet101-GeM, 3 scales + whitening; 0 = skip")
     ap.add_argument("--no-pipelined", action="store_true", help="(accepted for older command lines; no effect)")
     ap.add_argument("--profile", action="store_true", help="the headline loop only: --no-cpu-baseline --extract-images 0")
     ap.add_argument("--no-preflight", action="store_true", help="N > 1: skip tools/preflight_ranks.py (fresh child processes that check the "
@@ -226,6 +249,10 @@ def main():
     if args.profile:
         args.no_cpu_baseline, args.secondary = True, False
         args.extract_images = 0
+    if args.secondary:
+        args.full = True
+    if not args.full:
+        args.no_cpu_baseline, args.extract_images = True, 0
     if args.comm:
         os.environ["MDIR_AMD_COMM"] = args.comm
 
@@ -371,17 +398,25 @@ def main():
                 step()
             elapsed = timed_region()
 
-    # ---- results check + mAP (untimed) --------------------------------------
+    if args.dump_outputs:
+        if world == 1:
+            dump_outputs(args.dump_outputs, sc, rk)
+        elif rank == 0:         # rank 0's query rows of the global scores and ranking
+            dump_outputs(args.dump_outputs, keep["sc"].dense(), keep["rk"])
+
+    # ---- mAP (+ results check with --full; untimed) --------------------------
     extra = {}
     if world == 1:
         with contextlib.redirect_stdout(sys.stderr):      # stdout carries the one JSON line only
-            avg_s, _ = compute_map_and_print_from_scores("roxford5k", sc, gnd)       # counting kernel, no sort
             avg_r, _ = compute_map_and_print("roxford5k", rk.t(), gnd)               # from the full ranking
-        assert avg_s == avg_r, (avg_s, avg_r)
-        perm_ok, order_ok = verify_ranking(sc, rk)
-        assert perm_ok and order_ok, "the full ranking is not a stable descending permutation (perm %s, order %s)" % (perm_ok, order_ok)
-        extra["ranking_verified_on_device"] = "all %d rows: permutation, non-increasing scores, ascending ids inside ties" % NQ
-        assert bool((rk[:, 0].cpu() == torch.from_numpy(qid)).all()), "every query must retrieve its source row first"
+        if args.full:
+            with contextlib.redirect_stdout(sys.stderr):
+                avg_s, _ = compute_map_and_print_from_scores("roxford5k", sc, gnd)   # counting kernel, no sort
+            assert avg_s == avg_r, (avg_s, avg_r)
+            perm_ok, order_ok = verify_ranking(sc, rk)
+            assert perm_ok and order_ok, "the full ranking is not a stable descending permutation (perm %s, order %s)" % (perm_ok, order_ok)
+            extra["ranking_verified_on_device"] = "all %d rows: permutation, non-increasing scores, ascending ids inside ties" % NQ
+            assert bool((rk[:, 0].cpu() == torch.from_numpy(qid)).all()), "every query must retrieve its source row first"
         extra["map_medium"] = avg_r["map_medium"]
         kernel_ms = float(np.mean([a.elapsed_time(b) for a, b, _ in ev]))
         rank_ms = float(np.mean([b.elapsed_time(c) for _, b, c in ev]))          # the 12 launches of one full ranking, HIP events

@@ -118,6 +118,39 @@ def test_bench_launches_its_own_ranks():
     assert proc.returncode == 2 and "GPU(s)" in proc.stderr
 
 
+def test_bench_dump_outputs_repeat_and_equal_the_hot_path(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: no CPU baseline, no extraction leg, `--steps` timed steps): the sampled scores
+    (float32) and ranking ids (float64) of the last timed step, together under 64 MB; a second run with the same arguments
+    writes the same bits, and so does `dump_outputs` on the similarity + full ranking of the same inputs in this process."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from mdir_amd import ops
+    from mdir_amd.sharded import ShardedIndex
+    n = 150000
+    common = ["--rows", str(n), "--steps", "4", "--warmup", "1", "--dump-outputs"]
+    line = _bench(common + [str(tmp_path / "a")], {})
+    _bench(common + [str(tmp_path / "b")], {})
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and 0.0 < line["map_medium"] <= 1.0
+    assert "cpu_baseline" not in line and "descriptors_per_s" not in line and "secondary_configs" not in line
+    device = torch.device(DEV)
+    rows = bench.gen_rows(0, n, device)
+    qvecs, qid = bench.gen_queries(n, device)
+    bench.plant_positives(rows, 0, n, bench.synth_gnd(min(bench.N_ROXFORD, n)), qid, device)
+    sc = ShardedIndex(rows, "ND", n).index.scores(qvecs, "DN")
+    bench.dump_outputs(str(tmp_path / "c"), sc, ops.rank_full(sc))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["ranking.npy", "scores.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    for f in names:
+        got = np.load(tmp_path / "a" / f)
+        assert got.dtype == (np.float64 if f == "ranking.npy" else np.float32) and got.shape[0] == 70
+        np.testing.assert_array_equal(got, np.load(tmp_path / "b" / f))
+        np.testing.assert_array_equal(got, np.load(tmp_path / "c" / f))
+    ids = np.load(tmp_path / "a" / "ranking.npy")
+    assert np.array_equal(ids[:, 0], qid.astype(np.float64)) and ids.min() >= 0 and ids.max() < n
+    assert all(len(np.unique(r)) == r.size for r in ids)
+
+
 # ---------------------------------------------------------------- the two wave-rank forms, graph capture
 
 _RANK_FORMS_SCRIPT = r"""

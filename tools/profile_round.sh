@@ -10,7 +10,7 @@ timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -- 
 cp $W/stats/*/*_kernel_stats.csv $OUT/kernel_stats.csv
 head -1 $W/stats/*/*_kernel_trace.csv > $OUT/kernel_trace_mdx.csv; grep "mdx::" $W/stats/*/*_kernel_trace.csv | head -4000 >> $OUT/kernel_trace_mdx.csv
 if [ "${EXTRACT:-1}" = "1" ]; then
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats_x -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-pipelined --extract-images 16 > $OUT/stats_extract.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats_x -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary --no-pipelined --extract-images 16 > $OUT/stats_extract.log 2>&1
   cp $W/stats_x/*/*_kernel_stats.csv $OUT/kernel_stats_extract.csv
 fi
 for c in FETCH_SIZE WRITE_SIZE "SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_WAVES"; do
