@@ -395,6 +395,39 @@ int mdx_rank_count(const float *scores, int64_t n, int64_t nq, int64_t id_offset
                    const float *ref_scores, const int64_t *ref_ids, const int64_t *offsets,
                    int64_t total, int64_t *cnt, void *stream);
 
+/* --------------------------------------------------------------- re-ranking */
+
+/* The weighted gather-and-normalise behind alpha-weighted query expansion (alpha-QE) and database-side augmentation (DBA),
+ * the re-ranking of the GeM paper's protocol (Radenovic, Tolias, Chum, "Fine-tuning CNN image retrieval with no human
+ * annotation", TPAMI 2018).  Not in the reference (the vendored cirtorch does not ship it).
+ *
+ * For an output row q with neighbour ids ids[q, 0..k-1] and their similarities s[q, j]:
+ *
+ *   w_j   = s_j ** alpha   if s_j > 0   (alpha == 0 -> 1)
+ *           0              otherwise    (includes NaN)
+ *   v     = self_q (if a self row is given, weight 1, first) ; then for j = 0 .. k-1 in that order:
+ *           v = fmaf(w_j, rows[ids[q, j]], v)          elementwise, fp32
+ *   out_q = v / (||v||_2 + eps)                        eps = 1e-6: the project's L2N rule, zero row -> zero row
+ *
+ *  - An id outside [0, n) contributes nothing and is never dereferenced: the call is safe on any id array.
+ *  - alpha-QE, for queries Q against a database X (rows [N, D]):
+ *      (ids, s) = topk(Q.X^T, k), k' = min(k, N), mdx_topk's order (descending score, ascending id on ties);
+ *      Q' = aggregate(X, ids, s, self = Q); the final scores are Q'.X^T.
+ *    alpha = 0 is plain average QE.  In self-retrieval the query's own row is its own top neighbour.
+ *  - DBA of X: for every row i, (ids, s) = topk(x_i.X^T, k) -- the top-k includes i itself, no separate self term --
+ *    and x'_i = aggregate(X, ids, s, self = none), always read from the ORIGINAL X.  The result is a new matrix.
+ *  - With both: DBA first, then alpha-QE, which searches and aggregates over X'.  Queries are never DBA-augmented.
+ *  - Bit-determinism: every out_q is bit-identical run to run and does not depend on nq or on which other rows are in
+ *    the launch (one wave per row, fixed summation orders).
+ *
+ * rows [n, d] at a stride of ld >= d floats; ids int64 and sims fp32, both [nq, k] contiguous; self_rows [nq, d] at ld_self
+ * (NULL = no self term); out [nq, d] at ld_out.  All device pointers.  MDX_ERR_INVALID, nothing launched, for a NULL rows /
+ * ids / sims / out, n, d, nq or k < 1, a stride < d, alpha or eps negative or not finite, or out overlapping rows or
+ * self_rows.  With eps = 0 an all-zero row divides 0 by 0. */
+int mdx_knn_aggregate(const float *rows, int64_t n, int64_t d, int64_t ld, const int64_t *ids, const float *sims, int64_t nq,
+                      int64_t k, const float *self_rows, int64_t ld_self, float alpha, float l2n_eps, float *out, int64_t ld_out,
+                      void *stream);
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -589,6 +589,46 @@ def topk(scores, k, id_offset=0, workspace=None):
     return ids, vals
 
 
+def _rows(t, what):
+    """(pointer, row stride) of a 2-D fp32 CUDA matrix whose rows are contiguous (a row slice of a larger matrix is fine)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA/ROCm tensor: the MI355X path has no CPU fallback" % what)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be torch.float32, got %s" % (what, t.dtype))
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        raise ValueError("%s must be a 2-d matrix with contiguous rows" % what)
+    return _vp(t.data_ptr()), t.stride(0)
+
+
+def knn_aggregate(rows, ids, sims, alpha, self_rows=None, eps=1e-6, out=None):
+    """fp32 ``[nq, d]``: row q = the L2-normalised ``self_rows[q] + sum_j w_j rows[ids[q, j]]`` with
+    ``w_j = sims[q, j] ** alpha`` for a positive similarity and 0 otherwise (``mdx_knn_aggregate``; the contract, its
+    summation order and its bit-determinism are in ``include/mdx.h``).  ``ids`` int64 and ``sims`` fp32 are ``[nq, k]``
+    (what :func:`topk` returns); an id outside ``[0, n)`` contributes nothing.  ``rows``, ``self_rows`` and ``out`` may be
+    row slices of larger matrices; ``out`` must not overlap ``rows`` or ``self_rows``."""
+    rp, ld = _rows(rows, "rows")
+    n, d = rows.shape
+    ip = _dev(ids, torch.int64, "ids")
+    sp = _dev(sims, torch.float32, "sims")
+    if ids.dim() != 2 or tuple(sims.shape) != tuple(ids.shape):
+        raise ValueError("ids and sims must both be [nq, k], got %s and %s" % (tuple(ids.shape), tuple(sims.shape)))
+    nq, k = ids.shape
+    selfp, ld_self = None, d
+    if self_rows is not None:
+        selfp, ld_self = _rows(self_rows, "self_rows")
+        if tuple(self_rows.shape) != (nq, d):
+            raise ValueError("self_rows must be [%d,%d], got %s" % (nq, d, tuple(self_rows.shape)))
+    if out is None:
+        out = torch.empty((nq, d), dtype=torch.float32, device=rows.device)
+    elif tuple(out.shape) != (nq, d):
+        raise ValueError("out must be [%d,%d]" % (nq, d))
+    op, ld_out = _rows(out, "out")
+    with _on(rows):
+        check(_lib.lib().mdx_knn_aggregate(rp, n, d, ld, ip, sp, nq, k, selfp, ld_self, float(alpha), float(eps), op, ld_out,
+                                           _stream()), "mdx_knn_aggregate")
+    return out
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)

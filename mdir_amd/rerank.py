@@ -1,0 +1,105 @@
+"""Re-ranking of the revisited Oxford/Paris protocol: alpha-weighted query expansion (alpha-QE) and database-side
+augmentation (DBA), as the GeM paper defines them (Radenovic, Tolias, Chum, "Fine-tuning CNN image retrieval with no human
+annotation", TPAMI 2018).  Not in the reference: the vendored cirtorch does not ship either.
+
+Both are built from the library's own pieces -- the exact similarity (``mdx_scores_rowmajor`` or an index), the top-k of
+``mdx_topk`` (descending score, ascending id on ties) and the weighted gather-and-normalise ``mdx_knn_aggregate``, whose
+contract (weights ``s ** alpha`` for ``s > 0``, fp32 fma chain in neighbour order, L2N with eps 1e-6) is stated in
+``include/mdx.h``.  Everything stays on the device; nothing falls back to the CPU.
+"""
+import math
+
+import torch
+
+from . import _lib, ops
+
+DBA_MEMORY_CAP = 4 << 30        # bytes of [chunk, N] scores + top-k workspace one DBA chunk may hold
+
+
+def _check(k, alpha):
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("k must be an integer >= 1, got %r" % (k,))
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("alpha must be a finite number >= 0, got %r" % (alpha,))
+
+
+def _similarity(vecs, queries, index, compute, out=None):
+    """[nq, N] scores of row-major ``queries`` against the rows of ``vecs`` (or of ``index``, which holds the same rows)."""
+    if index is None:
+        if compute not in ("chain", "exact"):
+            raise ValueError("compute=%r multiplies an index: pass index=DescriptorIndex(vecs, 'ND')" % (compute,))
+        return ops.scores_rowmajor(vecs, queries, "ND", out=out)
+    return index.scores(queries, "ND", out=out, compute=compute)
+
+
+def query_expansion(qvecs, vecs, k, alpha, index=None, compute="chain"):
+    """alpha-QE of ``qvecs`` ``[Q, D]`` against the database ``vecs`` ``[N, D]`` (both row-major fp32 on the device).
+
+    ``(ids, s) = topk(Q.X^T, min(k, N))``, ``Q' = knn_aggregate(X, ids, s, alpha, self_rows=Q)``, and the returned scores
+    are ``Q'.X^T``.  ``alpha = 0`` is plain average query expansion.  Both similarity passes use the same mode: with no
+    ``index`` the exact chain reads ``vecs`` where it lies (``scores_rowmajor``); with an ``index`` (an fp16 shard, or the
+    split3 / split2 modes through ``compute``) both passes are ``index.scores``.  The neighbour rows always come from the
+    fp32 ``vecs``.  In self-retrieval (queries that are database rows, as on Tokyo) a query's own row is its own top
+    neighbour and is counted once more on top of the self term, as a naive numpy implementation does.
+
+    Returns ``(scores [Q, N], expanded queries [Q, D])``."""
+    _check(k, alpha)
+    if vecs.dim() != 2 or qvecs.dim() != 2 or qvecs.shape[1] != vecs.shape[1]:
+        raise ValueError("qvecs [Q, D] and vecs [N, D] expected, got %s and %s" % (tuple(qvecs.shape), tuple(vecs.shape)))
+    k = min(k, vecs.shape[0])
+    scores = _similarity(vecs, qvecs, index, compute)
+    ids, sims = ops.topk(scores, k)
+    expanded = ops.knn_aggregate(vecs, ids, sims, alpha, self_rows=qvecs)
+    return _similarity(vecs, expanded, index, compute, out=scores), expanded
+
+
+def _dba_bytes(n, chunk, k):
+    return chunk * n * 4 + ops.rank_workspace_bytes(n, chunk) + chunk * k * 12
+
+
+def dba_chunk(n, k, cap=DBA_MEMORY_CAP):
+    """Rows per DBA step: as many as keep the ``[chunk, N]`` scores, the top-k workspace and the neighbour lists under
+    ``cap`` bytes (at least one)."""
+    chunk = max(1, min(n, cap // max(1, _dba_bytes(n, 1, k))))
+    while chunk > 1 and _dba_bytes(n, chunk, k) > cap:
+        chunk = max(1, min(chunk - 1, chunk * cap // _dba_bytes(n, chunk, k)))
+    return chunk
+
+
+def database_augmentation(vecs, k, alpha, chunk=None, layout="ND"):
+    """DBA of the database ``vecs``: a NEW ``[N, D]`` row-major fp32 matrix whose row i is
+    ``knn_aggregate(X, topk(x_i.X^T, min(k, N)), alpha)`` with no separate self term (the top-k includes i itself), always
+    read from the original rows.  ``vecs`` is never written.
+
+    The exact fp32 chain, ``chunk`` rows at a time (scores_rowmajor, topk, knn_aggregate into the preallocated result);
+    the default chunk keeps each step under ``DBA_MEMORY_CAP`` bytes (:func:`dba_chunk`).  The result does not depend on
+    the chunk: the similarity and the top-k of a row do not depend on the other rows of the launch.  ``layout="DN"``
+    accepts the reference's ``[D, N]`` matrix through one transpose copy; the result is ``[N, D]`` either way."""
+    _check(k, alpha)
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
+        raise ValueError("chunk must be an integer >= 1, got %r" % (chunk,))
+    if layout in ("DN", "dim_major", _lib.MDX_DIM_MAJOR):
+        vecs = vecs.t().contiguous()
+    elif layout not in ("ND", "row_major", _lib.MDX_ROW_MAJOR):
+        raise ValueError("unknown layout %r" % (layout,))
+    if vecs.dim() != 2:
+        raise ValueError("vecs must be 2-d, got %s" % (tuple(vecs.shape),))
+    n, d = vecs.shape
+    k = min(k, n)
+    chunk = min(chunk or dba_chunk(n, k), n)
+    # the exact chain on the rows where they lie; a dimension that is not a multiple of 4 goes through an index of the same
+    # rows (same kernels, same bits: include/mdx.h mdx_scores_rowmajor)
+    index = None if d % 4 == 0 else ops.DescriptorIndex(vecs, "ND")
+    out = torch.empty((n, d), dtype=torch.float32, device=vecs.device)
+    scores = torch.empty((chunk, n), dtype=torch.float32, device=vecs.device)
+    workspace = ops._workspace(ops.rank_workspace_bytes(n, chunk), vecs.device)
+    try:
+        for i0 in range(0, n, chunk):
+            i1 = min(n, i0 + chunk)
+            block = _similarity(vecs, vecs[i0:i1], index, "chain", out=scores[:i1 - i0])
+            ids, sims = ops.topk(block, k, workspace=workspace)
+            ops.knn_aggregate(vecs, ids, sims, alpha, out=out[i0:i1])
+    finally:
+        if index is not None:
+            index.close()
+    return out

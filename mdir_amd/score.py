@@ -17,15 +17,19 @@ fp16 for the fp16 MFMA -- BASELINE.json configs[4].  ``similarity="split3"`` (cr
 the LABELLED split-precision form of the dot product on the same fp32 shard (three bf16 pieces per operand on the bf16
 MFMA: 0.75 of the exact kernel's time, scores within 2e-6 of it; ``"split2"``: two fp16 pieces with a scaled residual,
 block floating point, 0.63 of the exact kernel's time, same bound for data of ordinary dynamic range; default ``"exact"`` =
-the k-ordered fp32 chain).
+the k-ordered fp32 chain).  ``query_expansion: {k, alpha}`` and ``database_augmentation: {k, alpha}`` (criterion keys,
+not in the reference) add the re-ranking every table on the revisited protocol reports beside the raw numbers: alpha-QE of
+the queries and DBA of the database (``mdir_amd/rerank.py``); with both, DBA runs first and alpha-QE searches the augmented
+database.  Single-process only for now.
 """
 import gzip
 import json
 import lzma
+import math
 import os.path
 from collections import OrderedDict
 
-from . import ops
+from . import ops, rerank
 from .datasets import configdataset, get_data_root, initialize_transforms
 from .evaluate import compute_map_and_print, compute_map_and_print_from_scores
 from .networks import extract_vectors_device
@@ -93,6 +97,9 @@ class CirDatasetAp:
         self.similarity = params.pop("similarity", "exact")
         assert self.similarity in {"exact", "split3", "split2"}, self.similarity
         assert not (self.similarity != "exact" and self.storage != "f32"), "similarity: split3 / split2 multiply an fp32 shard"
+        # re-ranking (not in the reference): alpha-QE of the queries and DBA of the database, each {k, alpha}; None = off
+        self.query_expansion = _rerank_params(params.pop("query_expansion", None), "query_expansion")
+        self.database_augmentation = _rerank_params(params.pop("database_augmentation", None), "database_augmentation")
         if isinstance(self.dataset, dict):
             assert self.dataset.keys() == {"name", "queries", "db", "imgdir"}
             imgdir = self.dataset["imgdir"]
@@ -115,6 +122,9 @@ class CirDatasetAp:
 
     def __call__(self, network, device, logger):
         stopwatch = StopWatch()
+        if _world_size() > 1 and (self.query_expansion or self.database_augmentation):
+            raise ValueError("%s: query_expansion / database_augmentation re-rank in a single process for now; this run has "
+                             "%d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1:
             # one process per GPU (torchrun eval.py ...): every rank extracts its slice of the
             # database, which stays resident as its shard; same rows go to the logger on every rank
@@ -142,10 +152,16 @@ class CirDatasetAp:
             # one evaluation multiplies the database once: the exact product reads `vecs` [N,D] where it lies
             # (mdx_scores_rowmajor: same kernels and bits as on an index, no 8 GB re-tiled copy); the fp16 shard and the
             # split-precision modes need their own operand formats and build an index
+            if self.database_augmentation:
+                with range_("database_augmentation"):               # DBA first: the queries keep their own descriptors
+                    vecs = rerank.database_augmentation(vecs, **self.database_augmentation)
             direct = self.storage == "f32" and self.similarity == "exact" and vecs.shape[1] % 4 == 0
             index = None if direct else ops.DescriptorIndex(vecs, "ND", storage=self.storage)
             with range_("similarity"):
-                if direct:
+                if self.query_expansion:
+                    compute = "chain" if self.similarity == "exact" else self.similarity
+                    scores, _ = rerank.query_expansion(qvecs, vecs, index=index, compute=compute, **self.query_expansion)
+                elif direct:
                     scores = ops.scores_rowmajor(vecs, qvecs, "ND")     # [Q,N] = (vecs.T @ qvecs).T
                 else:
                     kw = {} if self.similarity == "exact" else {"compute": self.similarity}
@@ -170,6 +186,20 @@ class CirDatasetAp:
         for i, _ in enumerate(first_score):
             logger(i, len(first_score), "score", {x: scores_per_query[x][i] for x in scores_per_query},
                    "scalar/score")
+
+
+def _rerank_params(value, key):
+    """``{k, alpha}`` of a re-ranking criterion key, validated (None: the key is absent)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict) or set(value) != {"k", "alpha"}:
+        raise ValueError("%s: a mapping with exactly the keys k and alpha, got %r" % (key, value))
+    k, alpha = value["k"], value["alpha"]
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("%s: k must be an integer >= 1, got %r" % (key, k))
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("%s: alpha must be a finite number >= 0, got %r" % (key, alpha))
+    return {"k": k, "alpha": float(alpha)}
 
 
 def _rank_world():

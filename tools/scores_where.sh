@@ -8,7 +8,9 @@
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/where_r05; rm -rf $OUT; mkdir -p $OUT
 ABL=/tmp/mdx_ablate_src; rm -rf $ABL; mkdir -p $ABL/mdir_amd; cp -r $R/mdir_amd/csrc $ABL/mdir_amd/csrc; cp -r $R/include $ABL/include
 (cd $ABL/mdir_amd/csrc && patch -p1 < $R/tools/ablate/scores_kernel_ablate.patch) || exit 1
-SRC="mdx_index.hip mdx_rank.hip mdx_pool.hip mdx_trunk.hip mdx_jpeg.hip mdx_comm.hip mdx_gram.hip mdx_conv.hip mdx_clahe.hip"
+# the sources of libmdx.so as the Makefile lists them: a variant library must export everything mdir_amd/_lib.py binds
+SRC=$(sed -n 's/^SRC *= *//p' $R/mdir_amd/csrc/Makefile)
+[ -n "$SRC" ] || exit 1
 for v in NOLOAD NOLDSREAD "NOLOAD -DMDX_ABL_NOLDSREAD"; do
   n=$(echo $v | tr -d ' -' | sed 's/DMDX_ABL_//')
   [ -f $R/mdir_amd/libmdx_abl_$n.so ] || (cd $ABL/mdir_amd/csrc && /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-result -DMDX_ABL_$v -shared -o $R/mdir_amd/libmdx_abl_$n.so $SRC)
