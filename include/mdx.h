@@ -428,6 +428,59 @@ int mdx_knn_aggregate(const float *rows, int64_t n, int64_t d, int64_t ld, const
                       int64_t k, const float *self_rows, int64_t ld_self, float alpha, float l2n_eps, float *out, int64_t ld_out,
                       void *stream);
 
+/* Diffusion on a mutual kNN graph of the database (Iscen, Tolias, Avrithis, Furon, Chum, "Efficient diffusion on region
+ * manifolds", CVPR 2017; the "DFS" rows of Radenovic et al., "Revisiting Oxford and Paris", CVPR 2018).  Not in the
+ * reference.  Defaults of the paper's public release: k = 50, kq = 10, gamma = 3, alpha = 0.99, iters = 20, tol = 1e-6
+ * (the paper's values; not checked against published tables here).
+ *
+ * Graph of the database X [N, D] (L2-normalised fp32 rows), built once, offline like DBA:
+ *   L_i   = topk(x_i . X^T, min(k, N)) in mdx_topk's order (descending score, ascending id on ties); normally holds i itself
+ *   edge (i, j): j != i (by id), j in L_i and i in L_j (mutual neighbours); an id repeated in a list counts at its first
+ *   position only (mdx_topk's lists have no repeats)
+ *   w_ij  = max(s, 0) ** gamma (powf; NaN counts as 0), s = the similarity recorded in the list of min(i, j) (at the
+ *   first position of the other id): w_ij == w_ji
+ *   d_i   = sum_j w_ij, an fp32 sequential sum in L_i order;  r_i = 1 / sqrt(d_i + 1e-12)
+ *   S_ij  = w_ij * (r_lo * r_hi), lo = min(i, j), hi = max(i, j): S is exactly symmetric
+ *   stored as a compacted ELL: cols int32 [N, k] (row i's edges first, in L_i order; then -1), vals fp32 [N, k] (then 0),
+ *   counts int32 [N].  No row has more than k entries.
+ * Query q with first-stage scores s_q = q . X^T (any similarity mode):
+ *   seeds y_j = max(s_qj, 0) ** gamma for j in topk(s_q, min(kq, N)), 0 elsewhere (a repeated seed id keeps its last value)
+ *   CG on (I - alpha S) f = y, 0 <= alpha < 1, from f = 0, r = p = y, at most iters steps:
+ *     Ap_i = fmaf(-alpha, sum_e S_ie p_j(e), p_i)   (the sum an fp32 fma chain in the row's edge order)
+ *     a = rr / (p . Ap);  f += a p;  r -= a Ap;  rr' = r . r;  beta = rr' / rr;  p = r + beta p
+ *   A column stops once rr' <= (tol * tol) * (y . y) (fp32), decided on the device: from then on its step sizes are 0.
+ *   Nothing is read back and the launch sequence depends on iters only.  y = 0: f = 0, no step.
+ *   out[q, j] = f_j if f_j > 0, else s_qj - 3: rows the diffusion did not reach rank after every reached row, in their
+ *   first-stage order (ties: mdx_rank_full's rule).
+ *   residual[q] = sqrt(rr / y . y) at the end (0 when y = 0); steps[q] = the steps taken.
+ * Bit-determinism, as mdx_knn_aggregate: every output is bit-identical run to run, and a query's outputs do not depend on nq
+ * or on the other queries of the launch.  The dot products are sums over a fixed partition of the rows (independent of nq),
+ * one partial per partition and column, summed in a fixed order; no float atomics.
+ * Everything is legal under stream capture. */
+
+/* Bytes of device workspace of mdx_knn_graph (r = 1 / sqrt(d + 1e-12) per row); 0 for n < 1. */
+int64_t mdx_knn_graph_workspace(int64_t n);
+/* The graph from ids int64 and sims fp32, both [n, k] contiguous (what mdx_topk returns for the database against itself),
+ * into cols / vals [n, k] and counts [n].  Two launches (mutual test + weights + compaction + degree; normalisation).  An id
+ * outside [0, n) is never dereferenced and is no edge.  MDX_ERR_INVALID, nothing launched, for a NULL pointer, n or k < 1,
+ * n >= 2^31, gamma negative or not finite; MDX_ERR_WORKSPACE for fewer than mdx_knn_graph_workspace(n) bytes. */
+int mdx_knn_graph(const int64_t *ids, const float *sims, int64_t n, int64_t k, float gamma, int32_t *cols, float *vals,
+                  int32_t *counts, void *workspace, int64_t workspace_bytes, void *stream);
+/* Bytes of device workspace of mdx_diffusion: F, R, P, AP node-major [n, round_up(nq, 4)] fp32, the per-partition partials and
+ * the per-column CG state; 0 for n < 1, nq < 1 or nq > 256. */
+int64_t mdx_diffusion_workspace(int64_t n, int64_t nq);
+/* The solve for nq <= 256 queries: graph (cols, vals, counts) of mdx_knn_graph, width k; scores [nq, n] at a stride of
+ * ld_scores floats (the first-stage s_q); seed_ids int64 / seed_sims fp32 [nq, kq] (mdx_topk of the scores); out [nq, n] at
+ * ld_out, row-major for mdx_rank_full.  out may equal scores (with the same stride); any other overlap is refused.
+ * residual fp32 [nq] and steps int32 [nq] are optional (NULL).  A column outside [0, n) in cols is no edge, a seed id outside
+ * [0, n) no seed.  MDX_ERR_INVALID, nothing launched, for a NULL pointer, n, k, kq or nq < 1, nq > 256, n >= 2^31, a stride
+ * below n, gamma or tol negative or not finite, alpha outside [0, 1), iters < 1; MDX_ERR_WORKSPACE for fewer than
+ * mdx_diffusion_workspace(n, nq) bytes (16-byte aligned). */
+int mdx_diffusion(const int32_t *cols, const float *vals, const int32_t *counts, int64_t n, int64_t k, const float *scores,
+                  int64_t ld_scores, const int64_t *seed_ids, const float *seed_sims, int64_t nq, int64_t kq, float gamma,
+                  float alpha, int64_t iters, float tol, float *out, int64_t ld_out, float *residual, int32_t *steps,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -5,6 +5,7 @@ torch.distributed.  Every function here hands raw device pointers to the C ABI
 (include/mdx.h); nothing computes with torch ops and nothing falls back to the CPU.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -627,6 +628,94 @@ def knn_aggregate(rows, ids, sims, alpha, self_rows=None, eps=1e-6, out=None):
         check(_lib.lib().mdx_knn_aggregate(rp, n, d, ld, ip, sp, nq, k, selfp, ld_self, float(alpha), float(eps), op, ld_out,
                                            _stream()), "mdx_knn_aggregate")
     return out
+
+
+DIFFUSION_MAX_NQ = 256        # queries per mdx_diffusion launch (64 lanes x float4)
+
+
+def _finite(x, what, lo=0.0, hi=None):
+    """``x`` as a float, ValueError unless it is a finite real number in ``[lo, hi)`` (``hi`` None: no upper bound)."""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < lo or (hi is not None and x >= hi):
+        raise ValueError("%s must be a finite number in [%g, %s), got %r" % (what, lo, "inf" if hi is None else "%g" % hi, x))
+    return float(x)
+
+
+def knn_graph(ids, sims, gamma):
+    """The normalised mutual kNN graph of diffusion (``mdx_knn_graph``; the definition is in ``include/mdx.h``) from the
+    database's own top-k lists: ``ids`` int64 and ``sims`` fp32 ``[N, k]`` (what :func:`topk` returns for every row against
+    the whole database).  Returns ``(cols int32 [N, k], vals fp32 [N, k], counts int32 [N])``, row i's edges first in list
+    order.  An id outside ``[0, N)`` is no edge."""
+    gamma = _finite(gamma, "gamma")
+    ip = _dev(ids, torch.int64, "ids")
+    sp = _dev(sims, torch.float32, "sims")
+    if ids.dim() != 2 or tuple(sims.shape) != tuple(ids.shape):
+        raise ValueError("ids and sims must both be [N, k], got %s and %s" % (tuple(ids.shape), tuple(sims.shape)))
+    n, k = ids.shape
+    if n < 1 or k < 1:
+        raise ValueError("ids must be a non-empty [N, k], got %s" % (tuple(ids.shape),))
+    h = _lib.lib()
+    cols = torch.empty((n, k), dtype=torch.int32, device=ids.device)
+    vals = torch.empty((n, k), dtype=torch.float32, device=ids.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    nbytes = h.mdx_knn_graph_workspace(n)
+    ws = _workspace(nbytes, ids.device)
+    with _on(ids):
+        check(h.mdx_knn_graph(ip, sp, n, k, gamma, _vp(cols.data_ptr()), _vp(vals.data_ptr()), _vp(counts.data_ptr()),
+                              _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_knn_graph")
+    return cols, vals, counts
+
+
+def diffusion(graph, scores, seed_ids, seed_sims, gamma, alpha, iters, tol, out=None, return_residual=False):
+    """Diffusion scores ``[nq, N]`` (``mdx_diffusion``: CG on ``(I - alpha S) f = y``, the definition in ``include/mdx.h``):
+    ``f_j`` where positive, else ``scores - 3``.  ``graph`` is ``(cols, vals, counts)`` of :func:`knn_graph` or an object
+    with those attributes; ``scores`` the first-stage ``[nq, N]`` scores (rows contiguous; a row slice is fine);
+    ``seed_ids`` int64 / ``seed_sims`` fp32 ``[nq, kq]`` (:func:`topk` of the scores).  ``out`` may be ``scores`` (in
+    place).  More than 256 queries run in groups of 256, which gives the same bits (a query's outputs do not depend on the
+    other queries of a launch).  With ``return_residual``: ``(out, residual fp32 [nq], steps int32 [nq])``."""
+    cols, vals, counts = graph if isinstance(graph, tuple) else (graph.cols, graph.vals, graph.counts)
+    gamma = _finite(gamma, "gamma")
+    alpha = _finite(alpha, "alpha", 0.0, 1.0)
+    tol = _finite(tol, "tol")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError("iters must be an integer >= 1, got %r" % (iters,))
+    _dev(cols, torch.int32, "cols")
+    _dev(vals, torch.float32, "vals")
+    _dev(counts, torch.int32, "counts")
+    if cols.dim() != 2 or tuple(vals.shape) != tuple(cols.shape) or tuple(counts.shape) != (cols.shape[0],):
+        raise ValueError("graph: cols / vals [N, k] and counts [N] expected, got %s, %s, %s"
+                         % (tuple(cols.shape), tuple(vals.shape), tuple(counts.shape)))
+    n, k = cols.shape
+    sp, ld = _rows(scores, "scores")
+    nq = scores.shape[0]
+    if scores.shape[1] != n:
+        raise ValueError("scores must be [nq, %d], got %s" % (n, tuple(scores.shape)))
+    _dev(seed_ids, torch.int64, "seed_ids")
+    _dev(seed_sims, torch.float32, "seed_sims")
+    if seed_ids.dim() != 2 or tuple(seed_sims.shape) != tuple(seed_ids.shape) or seed_ids.shape[0] != nq:
+        raise ValueError("seed_ids and seed_sims must both be [%d, kq], got %s and %s"
+                         % (nq, tuple(seed_ids.shape), tuple(seed_sims.shape)))
+    kq = seed_ids.shape[1]
+    if out is None:
+        out = torch.empty((nq, n), dtype=torch.float32, device=scores.device)
+    elif tuple(out.shape) != (nq, n):
+        raise ValueError("out must be [%d,%d]" % (nq, n))
+    _, ld_out = _rows(out, "out")
+    residual = torch.empty((nq,), dtype=torch.float32, device=scores.device) if return_residual else None
+    steps = torch.empty((nq,), dtype=torch.int32, device=scores.device) if return_residual else None
+    h = _lib.lib()
+    group = min(nq, DIFFUSION_MAX_NQ)
+    nbytes = h.mdx_diffusion_workspace(n, group)
+    ws = _workspace(nbytes, scores.device)
+    with _on(scores):
+        for q0 in range(0, nq, group):
+            q1 = min(nq, q0 + group)
+            check(h.mdx_diffusion(_vp(cols.data_ptr()), _vp(vals.data_ptr()), _vp(counts.data_ptr()), n, k,
+                                  _vp(scores[q0].data_ptr()), ld, _vp(seed_ids[q0].data_ptr()), _vp(seed_sims[q0].data_ptr()),
+                                  q1 - q0, kq, gamma, alpha, iters, tol, _vp(out[q0].data_ptr()), ld_out,
+                                  _vp(residual[q0].data_ptr()) if return_residual else None,
+                                  _vp(steps[q0].data_ptr()) if return_residual else None, _vp(ws.data_ptr()), ws.numel(),
+                                  _stream()), "mdx_diffusion")
+    return (out, residual, steps) if return_residual else out
 
 
 def _csr(id_lists, device):

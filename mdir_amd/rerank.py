@@ -1,6 +1,7 @@
 """Re-ranking of the revisited Oxford/Paris protocol: alpha-weighted query expansion (alpha-QE) and database-side
 augmentation (DBA), as the GeM paper defines them (Radenovic, Tolias, Chum, "Fine-tuning CNN image retrieval with no human
-annotation", TPAMI 2018).  Not in the reference: the vendored cirtorch does not ship either.
+annotation", TPAMI 2018), and diffusion on a mutual kNN graph of the database (Iscen et al., "Efficient diffusion on region
+manifolds", CVPR 2017).  Not in the reference: the vendored cirtorch ships none of them.
 
 Both are built from the library's own pieces -- the exact similarity (``mdx_scores_rowmajor`` or an index), the top-k of
 ``mdx_topk`` (descending score, ascending id on ties) and the weighted gather-and-normalise ``mdx_knn_aggregate``, whose
@@ -103,3 +104,103 @@ def database_augmentation(vecs, k, alpha, chunk=None, layout="ND"):
         if index is not None:
             index.close()
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------ diffusion
+
+DIFFUSION_DEFAULTS = {"k": 50, "kq": 10, "gamma": 3.0, "alpha": 0.99, "iters": 20, "tol": 1e-6}   # the paper's release
+
+
+def _check_int(x, what):
+    if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+        raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+
+
+def _check_real(x, what, upper=None):
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0 or \
+            (upper is not None and x >= upper):
+        raise ValueError("%s must be a finite number >= 0%s, got %r" % (what, "" if upper is None else " and < %g" % upper, x))
+
+
+class DiffusionGraph:
+    """The normalised mutual kNN graph of the database ``vecs`` ``[N, D]`` that :func:`diffusion` solves on
+    (``mdx_knn_graph``; definition in ``include/mdx.h``).  Built once per database, like DBA: the exact fp32 chain
+    ``chunk`` rows at a time (scores_rowmajor, topk of ``min(k, N)``), under the DBA memory cap for the chunk
+    (:func:`dba_chunk`), then the graph kernel on the whole ``[N, k]`` lists.  The lists do not depend on the chunk.
+
+    Attributes: ``cols`` int32 / ``vals`` fp32 ``[N, k]``, ``counts`` int32 ``[N]``, ``n``, ``k`` (``min(k, N)``),
+    ``gamma``.  ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy."""
+
+    def __init__(self, vecs, k=50, gamma=3.0, chunk=None, layout="ND"):
+        _check_int(k, "k")
+        _check_real(gamma, "gamma")
+        if chunk is not None:
+            _check_int(chunk, "chunk")
+        if layout in ("DN", "dim_major", _lib.MDX_DIM_MAJOR):
+            vecs = vecs.t().contiguous()
+        elif layout not in ("ND", "row_major", _lib.MDX_ROW_MAJOR):
+            raise ValueError("unknown layout %r" % (layout,))
+        if vecs.dim() != 2:
+            raise ValueError("vecs must be 2-d, got %s" % (tuple(vecs.shape),))
+        n, d = vecs.shape
+        k = min(k, n)
+        chunk = min(chunk or dba_chunk(n, k), n)
+        index = None if d % 4 == 0 else ops.DescriptorIndex(vecs, "ND")      # same kernels, same bits (see DBA)
+        ids = torch.empty((n, k), dtype=torch.int64, device=vecs.device)
+        sims = torch.empty((n, k), dtype=torch.float32, device=vecs.device)
+        scores = torch.empty((chunk, n), dtype=torch.float32, device=vecs.device)
+        workspace = ops._workspace(ops.rank_workspace_bytes(n, chunk), vecs.device)
+        try:
+            for i0 in range(0, n, chunk):
+                i1 = min(n, i0 + chunk)
+                block = _similarity(vecs, vecs[i0:i1], index, "chain", out=scores[:i1 - i0])
+                bi, bs = ops.topk(block, k, workspace=workspace)
+                ids[i0:i1] = bi
+                sims[i0:i1] = bs
+        finally:
+            if index is not None:
+                index.close()
+        del scores, workspace
+        self.cols, self.vals, self.counts = ops.knn_graph(ids, sims, gamma)
+        self.n, self.k, self.gamma = n, k, float(gamma)
+
+    def edges(self):
+        """Stored (directed) edges: twice the number of mutual pairs.  Reads the counts back (synchronises)."""
+        return int(self.counts.sum(dtype=torch.int64).item())
+
+    def close(self):
+        self.cols = self.vals = self.counts = None
+
+
+def diffusion(qvecs, vecs, graph=None, kq=10, alpha=0.99, iters=20, tol=1e-6, index=None, compute="chain", scores=None,
+              return_residual=False):
+    """Diffusion scores ``[Q, N]`` of the queries ``qvecs`` ``[Q, D]`` on the database ``vecs`` ``[N, D]``
+    (``mdx_diffusion``; definition in ``include/mdx.h``): seeds ``max(s, 0) ** gamma`` at the ``min(kq, N)`` best
+    first-stage scores, CG on ``(I - alpha S) f = y`` for at most ``iters`` steps, then ``f`` where positive and the
+    first-stage score minus 3 elsewhere, so that rows the diffusion did not reach rank last, in first-stage order.
+
+    ``graph`` is a :class:`DiffusionGraph` of ``vecs`` (built here with its defaults when None; pass one to reuse it across
+    batches); its ``gamma`` also weights the seeds.  The first-stage scores come from ``scores`` when given (never
+    written), else from the similarity of ``vecs`` or ``index`` in mode ``compute`` (as :func:`query_expansion`).
+    With ``return_residual``: ``(scores, residual [Q], steps [Q])``, the final ``||r|| / ||y||`` and the steps taken."""
+    _check_int(kq, "kq")
+    _check_real(alpha, "alpha", upper=1.0)
+    _check_int(iters, "iters")
+    _check_real(tol, "tol")
+    if vecs.dim() != 2 or qvecs.dim() != 2 or qvecs.shape[1] != vecs.shape[1]:
+        raise ValueError("qvecs [Q, D] and vecs [N, D] expected, got %s and %s" % (tuple(qvecs.shape), tuple(vecs.shape)))
+    n = vecs.shape[0]
+    if graph is None:
+        graph = DiffusionGraph(vecs)
+    if graph.n != n:
+        raise ValueError("graph has %d rows, the database %d" % (graph.n, n))
+    if scores is None:
+        first = _similarity(vecs, qvecs, index, compute)
+        out = first                                        # ours: solved in place
+    else:
+        if tuple(scores.shape) != (qvecs.shape[0], n):
+            raise ValueError("scores must be [%d, %d], got %s" % (qvecs.shape[0], n, tuple(scores.shape)))
+        first, out = scores, None
+    seed_ids, seed_sims = ops.topk(first, min(kq, n))
+    return ops.diffusion(graph, first, seed_ids, seed_sims, graph.gamma, alpha, iters, tol, out=out,
+                         return_residual=return_residual)

@@ -20,7 +20,9 @@ block floating point, 0.63 of the exact kernel's time, same bound for data of or
 the k-ordered fp32 chain).  ``query_expansion: {k, alpha}`` and ``database_augmentation: {k, alpha}`` (criterion keys,
 not in the reference) add the re-ranking every table on the revisited protocol reports beside the raw numbers: alpha-QE of
 the queries and DBA of the database (``mdir_amd/rerank.py``); with both, DBA runs first and alpha-QE searches the augmented
-database.  Single-process only for now.
+database.  Single-process only for now.  ``diffusion: {k, kq, gamma, alpha, iters, tol}`` (criterion key, every
+sub-key optional, defaults of the paper's release) re-ranks by diffusion on a mutual kNN graph of the database
+(``rerank.diffusion``), after DBA when both are set; not together with query_expansion; single-process only.
 """
 import gzip
 import json
@@ -100,6 +102,10 @@ class CirDatasetAp:
         # re-ranking (not in the reference): alpha-QE of the queries and DBA of the database, each {k, alpha}; None = off
         self.query_expansion = _rerank_params(params.pop("query_expansion", None), "query_expansion")
         self.database_augmentation = _rerank_params(params.pop("database_augmentation", None), "database_augmentation")
+        # diffusion on a mutual kNN graph of the database (not in the reference): {k, kq, gamma, alpha, iters, tol}; None = off
+        self.diffusion = _diffusion_params(params.pop("diffusion", None))
+        if self.diffusion and self.query_expansion:
+            raise ValueError("diffusion together with query_expansion is not supported: choose one")
         if isinstance(self.dataset, dict):
             assert self.dataset.keys() == {"name", "queries", "db", "imgdir"}
             imgdir = self.dataset["imgdir"]
@@ -124,6 +130,9 @@ class CirDatasetAp:
         stopwatch = StopWatch()
         if _world_size() > 1 and (self.query_expansion or self.database_augmentation):
             raise ValueError("%s: query_expansion / database_augmentation re-rank in a single process for now; this run has "
+                             "%d ranks" % (self.dataset, _world_size()))
+        if _world_size() > 1 and self.diffusion:
+            raise ValueError("%s: diffusion re-ranks in a single process (the graph spans the whole database); this run has "
                              "%d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1:
             # one process per GPU (torchrun eval.py ...): every rank extracts its slice of the
@@ -166,6 +175,13 @@ class CirDatasetAp:
                 else:
                     kw = {} if self.similarity == "exact" else {"compute": self.similarity}
                     scores = index.scores(qvecs, "ND", **kw)
+            if self.diffusion:
+                p = self.diffusion
+                with range_("diffusion"):
+                    graph = rerank.DiffusionGraph(vecs, k=p["k"], gamma=p["gamma"])
+                    scores = rerank.diffusion(qvecs, vecs, graph, kq=p["kq"], alpha=p["alpha"], iters=p["iters"],
+                                              tol=p["tol"], scores=scores)
+                    graph.close()
             if self.ranking == "full":
                 with range_("ranking"):
                     ranks = ops.rank_full(scores)                   # [Q,N] = argsort(-scores, axis=0).T
@@ -200,6 +216,31 @@ def _rerank_params(value, key):
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
         raise ValueError("%s: alpha must be a finite number >= 0, got %r" % (key, alpha))
     return {"k": k, "alpha": float(alpha)}
+
+
+def _diffusion_params(value):
+    """``{k, kq, gamma, alpha, iters, tol}`` of the ``diffusion`` criterion key, each optional (the defaults of
+    ``rerank.DIFFUSION_DEFAULTS``), validated (None: the key is absent)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict):
+        raise ValueError("diffusion: a mapping with the optional keys k, kq, gamma, alpha, iters, tol, got %r" % (value,))
+    unknown = set(value) - set(rerank.DIFFUSION_DEFAULTS)
+    if unknown:
+        raise ValueError("diffusion: unknown keys %s (allowed: k, kq, gamma, alpha, iters, tol)" % sorted(unknown))
+    out = dict(rerank.DIFFUSION_DEFAULTS, **value)
+    for key in ("k", "kq", "iters"):
+        x = out[key]
+        if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+            raise ValueError("diffusion: %s must be an integer >= 1, got %r" % (key, x))
+    for key, upper in (("gamma", None), ("alpha", 1.0), ("tol", None)):
+        x = out[key]
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0 or \
+                (upper is not None and x >= upper):
+            raise ValueError("diffusion: %s must be a finite number >= 0%s, got %r"
+                             % (key, "" if upper is None else " and < %g" % upper, x))
+        out[key] = float(x)
+    return out
 
 
 def _rank_world():
