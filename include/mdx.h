@@ -481,6 +481,48 @@ int mdx_diffusion(const int32_t *cols, const float *vals, const int32_t *counts,
                   float alpha, int64_t iters, float tol, float *out, int64_t ld_out, float *residual, int32_t *steps,
                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Truncated diffusion: each query's CG on the subgraph induced by its top-R first-stage rows, renormalised on that subgraph
+ * (whether the paper's release renormalises is not checked here), one workgroup per query with the whole state in LDS.  An opt-in mode beside mdx_diffusion, whose
+ * graph it shares through the unnormalised weights:
+ *   W     the affinity of mdx_knn_graph before normalisation: the same edges in the same compacted ELL order,
+ *         w_ij = max(s, 0) ** gamma as defined there (mdx_knn_graph_weights)
+ *   R     = min(truncate, N), 1 <= R <= MDX_DIFFUSION_MAX_R
+ *   T_q   = mdx_topk(s_q, R): ids t_0 .. t_{R-1} and their scores, in mdx_topk's order; an id repeated in T_q is a node at its
+ *         first position only, an id outside [0, N) is no node
+ *   seeds the first min(kq, R) entries of T_q (by that order exactly topk(s_q, kq), the seeds of mdx_diffusion),
+ *         y_a = max(s, 0) ** gamma
+ *   edges (a, b) for t_b in the ELL row of t_a, kept in that row's order; d^R_a = fp32 sequential sum of the kept w in that
+ *         order; r_a = 1 / sqrt(d^R_a + 1e-12); S^R_ab = w * (r_a * r_b): exactly symmetric, and with R = N bit-identical to
+ *         mdx_knn_graph's S
+ *   CG on (I - alpha S^R) f = y over the R unknowns: mdx_diffusion's recurrence, fp32 fma-chain SpMV in edge order, device
+ *   stop rule (rr' <= tol^2 * y . y) and iters cap
+ *   out[q, t_a] = f_a where f_a > 0; every other entry, in T_q or not, s_qj - 3.  residual / steps as mdx_diffusion.
+ * The dot products are per-thread fma partials over fixed rows, then a fixed-order reduction inside the query's workgroup:
+ * every output is bit-identical run to run and independent of nq and of the other queries.  No float atomics; nothing is read
+ * back; legal under stream capture.  nq is unbounded (one workgroup per query). */
+#define MDX_DIFFUSION_MAX_R 4096
+
+/* W of the graph: cols and counts bit-identical to mdx_knn_graph's, w [n, k] fp32 the weights before normalisation (then 0).
+ * Launch 1 of mdx_knn_graph alone; same arguments, checks and workspace (mdx_knn_graph_workspace(n) bytes). */
+int mdx_knn_graph_weights(const int64_t *ids, const float *sims, int64_t n, int64_t k, float gamma, int32_t *cols, float *w,
+                          int32_t *counts, void *workspace, int64_t workspace_bytes, void *stream);
+/* Bytes of device workspace of mdx_diffusion_truncated: per query the kept edges (int32 local column + fp32 value) [k, r], the
+ * edge counts and f [r]: nq * (round_up(8 k r, 256) + 2 round_up(4 r, 256)).  0 for n, k, nq or r < 1, k > 2^20, nq >= 2^31,
+ * r > MDX_DIFFUSION_MAX_R or r > n. */
+int64_t mdx_diffusion_truncated_workspace(int64_t n, int64_t k, int64_t nq, int64_t r);
+/* The truncated solve: (cols, w, counts) of mdx_knn_graph_weights, width k; scores [nq, n] at ld_scores (the first-stage s_q);
+ * top_ids int64 / top_sims fp32 [nq, r] contiguous (mdx_topk of the scores, k = r); out [nq, n] at ld_out (may equal scores
+ * with the same stride; any other overlap is refused); residual fp32 [nq] and steps int32 [nq] optional (NULL).
+ * MDX_ERR_INVALID, nothing launched, for a NULL pointer, n, k, nq, r or kq < 1, r > MDX_DIFFUSION_MAX_R or r > n,
+ * n >= 2^31, k > 2^20, nq * ceil(n / 4096) >= 2^31, a stride below n, gamma or tol negative or not finite, alpha outside
+ * [0, 1), iters < 1, out overlapping scores; MDX_ERR_WORKSPACE for fewer than mdx_diffusion_truncated_workspace(n, k, nq, r)
+ * bytes (16-byte aligned).  Three launches: the solve (one workgroup per query), out = s - 3, the scatter of f > 0. */
+int mdx_diffusion_truncated(const int32_t *cols, const float *w, const int32_t *counts, int64_t n, int64_t k,
+                            const float *scores, int64_t ld_scores, const int64_t *top_ids, const float *top_sims, int64_t nq,
+                            int64_t r, int64_t kq, float gamma, float alpha, int64_t iters, float tol, float *out,
+                            int64_t ld_out, float *residual, int32_t *steps, void *workspace, int64_t workspace_bytes,
+                            void *stream);
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

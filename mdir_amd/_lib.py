@@ -101,6 +101,10 @@ def _declare(lib):
         "mdx_knn_graph": (i32, [p, p, i64, i64, f32, p, p, p, p, i64, p]),
         "mdx_diffusion_workspace": (i64, [i64, i64]),
         "mdx_diffusion": (i32, [p, p, p, i64, i64, p, i64, p, p, i64, i64, f32, f32, i64, f32, p, i64, p, p, p, i64, p]),
+        "mdx_knn_graph_weights": (i32, [p, p, i64, i64, f32, p, p, p, p, i64, p]),
+        "mdx_diffusion_truncated_workspace": (i64, [i64, i64, i64, i64]),
+        "mdx_diffusion_truncated": (i32, [p, p, p, i64, i64, p, i64, p, p, i64, i64, i64, f32, f32, i64, f32, p, i64, p, p, p, i64,
+                                          p]),
         "mdx_conv1x1_transpose_weights": (i32, [p, i64, i64, p, p]),
         "mdx_conv1x1_bn_act": (i32, [p, p, i64, i64, i64, i64, p, p, p, p, f32, p, i32, p, p]),
         "mdx_gram_f64_workspace": (i64, [i64, i64]),
@@ -136,7 +140,8 @@ EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac
            "mdx_index_create", "mdx_index_create_ex", "mdx_index_bytes", "mdx_index_create_in", "mdx_index_destroy", "mdx_index_info", "mdx_scores_workspace",
            "mdx_scores", "mdx_scores_rowmajor", "mdx_scores_workspace_ex", "mdx_scores_ex", "mdx_rank_workspace", "mdx_rank_full", "mdx_rank_full_segments", "mdx_topk", "mdx_rank_of", "mdx_rank_positions",
            "mdx_gather_scores", "mdx_rank_count", "mdx_knn_aggregate", "mdx_knn_graph_workspace", "mdx_knn_graph",
-           "mdx_diffusion_workspace", "mdx_diffusion", "mdx_conv1x1_transpose_weights", "mdx_conv1x1_bn_act", "mdx_clahe_workspace", "mdx_clahe_u8_to_chw", "mdx_gram_f64_workspace", "mdx_gram_f64", "mdx_project_f64_workspace", "mdx_project_f64", "mdx_l2n_cols_f64", "mdx_comm_unique_id", "mdx_comm_init",
+           "mdx_diffusion_workspace", "mdx_diffusion", "mdx_knn_graph_weights", "mdx_diffusion_truncated_workspace",
+           "mdx_diffusion_truncated", "mdx_conv1x1_transpose_weights", "mdx_conv1x1_bn_act", "mdx_clahe_workspace", "mdx_clahe_u8_to_chw", "mdx_gram_f64_workspace", "mdx_gram_f64", "mdx_project_f64_workspace", "mdx_project_f64", "mdx_l2n_cols_f64", "mdx_comm_unique_id", "mdx_comm_init",
            "mdx_comm_destroy", "mdx_comm_info", "mdx_query_bounds", "mdx_allgather_scores", "mdx_exchange_scores",
            "mdx_p2p_create", "mdx_p2p_connect", "mdx_p2p_connect_ptrs", "mdx_p2p_base", "mdx_p2p_bytes", "mdx_scores_p2p", "mdx_p2p_close_step",
            "mdx_p2p_status", "mdx_p2p_destroy")

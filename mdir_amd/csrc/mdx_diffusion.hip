@@ -18,6 +18,18 @@
 // The partials use a fixed partition of the rows (PART rows per workgroup, independent of nq) and are summed in one fixed
 // order, so every output is bit-identical from run to run and a column's bits do not depend on the other columns of the
 // launch.  No float atomics.  Nothing is read back to the host and the launch sequence depends on iters only.
+// mdx_diffusion_truncated: each query's CG on the subgraph induced by its top-R first-stage rows, one workgroup of 1024
+// threads per query, every vector in LDS:
+//   (a) the R ids with their local positions as 64-bit keys (id << 32 | position), bitonic-sorted in LDS; an edge's
+//       membership is a binary search; a repeated id is a node at its first position only, an id outside [0, n) is none;
+//   (b) one wave per local row: the row's ELL entries in order, the in-set edges compacted by ballot into the per-query
+//       workspace as (local column, w), stored edge-major [k][R] (lane l of a wave reads row a + l: one coalesced load per
+//       edge slot), the degree an fp32 sequential sum in edge order; then S = w * (r_a * r_b) in place;
+//   (c) CG with r, f, p, Ap in LDS, one thread per row (rows t, t + 1024, ...), the row's SpMV an fp32 fma chain in edge
+//       order with the edges streamed from the workspace (L2 / MALL resident);
+//   (d) the dot products: per-thread fma partials over the thread's rows, a butterfly inside each wave, the 16 wave sums in
+//       wave order: fixed, so a query's bits do not depend on the other queries;
+//   (e) f [nq, R] to the workspace.  Two output launches: out = s - 3 over [nq, n], then the positive f scattered to t_a.
 #include <math.h>
 
 #include "mdx_common.h"
@@ -380,6 +392,278 @@ __global__ __launch_bounds__(256) void diffusion_final_kernel(const float *__res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- truncated solve
+
+constexpr int TRD_THREADS = 1024;                                 // one workgroup per query
+constexpr int TRD_WAVES = TRD_THREADS / 64;
+constexpr int TRD_ROWS = MDX_DIFFUSION_MAX_R / TRD_THREADS;       // local rows per thread at most
+constexpr int TRD_GATHER = 8;                                     // edges in flight per thread in the SpMV
+constexpr uint32_t TRD_NONE = 0x7FFFFFFFu;                        // key id of a non-node (no column equals it: n < 2^31)
+static_assert(MDX_DIFFUSION_MAX_R % TRD_THREADS == 0, "rows per thread");
+
+__host__ __device__ inline int64_t trd_round(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+__host__ __device__ inline int64_t trd_pow2(int64_t r)
+{
+    int64_t p = 1;
+    while (p < r) p <<= 1;
+    return p;
+}
+
+// bytes of dynamic LDS: keys [P] u64, then rinv, f, r, p, ap [round_up(R, 4)] fp32, then the 2 x 16 wave sums
+__host__ __device__ inline int64_t trd_lds(int64_t r) { return 8 * trd_pow2(r) + 5 * 4 * trd_round(r, 4) + 2 * TRD_WAVES * 4; }
+
+// per query: edges int2 [k][R] (local column, w then S), edge counts int32 [R], f fp32 [R]
+__host__ __device__ inline int64_t trd_edges_bytes(int64_t k, int64_t r) { return trd_round(k * r * 8, 256); }
+__host__ __device__ inline int64_t trd_query_bytes(int64_t k, int64_t r) { return trd_edges_bytes(k, r) + 2 * trd_round(r * 4, 256); }
+
+// the sum of v over the workgroup, the same bits in every thread: a butterfly in the wave, then the wave sums in order
+__device__ __forceinline__ float trd_block_sum(float v, float *red)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = red[0];
+#pragma unroll
+    for (int w = 1; w < TRD_WAVES; ++w) s += red[w];
+    return s;
+}
+
+__global__ __launch_bounds__(TRD_THREADS) void diffusion_truncated_solve_kernel(
+    const int32_t *__restrict__ cols, const float *__restrict__ wts, const int32_t *__restrict__ counts, int64_t n, int64_t k,
+    const int64_t *__restrict__ top_ids, const float *__restrict__ top_sims, int r, int64_t kq, float gamma, float alpha,
+    int64_t iters, float tol2, char *__restrict__ ws, float *__restrict__ residual, int32_t *__restrict__ steps_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t q = blockIdx.x;
+    const int P = (int)trd_pow2(r), rp = (int)trd_round(r, 4);
+    uint64_t *keys = (uint64_t *)lds;
+    float *rinv = (float *)(lds + 8 * P), *fv = rinv + rp, *rv = fv + rp, *pv = rv + rp, *apv = pv + rp;
+    float *red = apv + rp;
+    int *node = (int *)apv;                                       // until the CG starts: 1 = a node, 0 = none
+    const int64_t *ids = top_ids + q * r;
+    char *wq = ws + q * trd_query_bytes(k, r);
+    int2 *edges = (int2 *)wq;
+    int32_t *ecount = (int32_t *)(wq + trd_edges_bytes(k, r));
+    float *F = (float *)(wq + trd_edges_bytes(k, r) + trd_round((int64_t)r * 4, 256));
+
+    // (a) keys and the bitonic sort (the keys are distinct: the order is fixed)
+    for (int i = t; i < P; i += TRD_THREADS) {
+        uint32_t id = TRD_NONE;
+        if (i < r) {
+            const int64_t g = ids[i];
+            if (g >= 0 && g < n) id = (uint32_t)g;
+        }
+        keys[i] = (uint64_t)id << 32 | (uint32_t)i;
+    }
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int i = t; i < P / 2; i += TRD_THREADS) {
+                const int lo = 2 * stride * (i / stride) + (i % stride), hi = lo + stride;
+                const uint64_t a = keys[lo], b = keys[hi];
+                if ((a > b) == ((lo & size) == 0)) {
+                    keys[lo] = b;
+                    keys[hi] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < P; i += TRD_THREADS) {
+        const uint64_t key = keys[i];
+        const uint32_t pos = (uint32_t)key, id = (uint32_t)(key >> 32);
+        if (pos < (uint32_t)r) node[pos] = id != TRD_NONE && (i == 0 || (uint32_t)(keys[i - 1] >> 32) != id);
+    }
+    __syncthreads();
+
+    // (b) the in-set edges of every node's ELL row, in row order; the degree; r = 1 / sqrt(d + 1e-12)
+    for (int a = wave; a < r; a += TRD_WAVES) {
+        int64_t cnt = 0, i = 0;
+        if (node[a]) {
+            i = ids[a];
+            cnt = counts[i];
+            cnt = cnt < 0 ? 0 : (cnt > k ? k : cnt);
+        }
+        int c = 0;
+        float deg = 0.0f;
+        for (int64_t eb = 0; eb < cnt; eb += 64) {
+            const int64_t e = eb + lane;
+            int b = -1;
+            float w = 0.0f;
+            if (e < cnt) {
+                const int64_t j = cols[i * k + e];
+                if (j >= 0 && j < n) {                            // lower bound of (j, 0) among the keys
+                    const uint64_t want = (uint64_t)j << 32;
+                    int lo = 0, len = P;
+                    while (len > 0) {
+                        const int half = len >> 1;
+                        if (keys[lo + half] < want) {
+                            lo += half + 1;
+                            len -= half + 1;
+                        } else {
+                            len = half;
+                        }
+                    }
+                    if (lo < P && (uint32_t)(keys[lo] >> 32) == (uint32_t)j) b = (int)(uint32_t)keys[lo];
+                }
+                if (b >= 0) w = wts[i * k + e];
+            }
+            uint64_t mask = __ballot(b >= 0);
+            if (b >= 0) {
+                const int pos = c + __builtin_popcountll(mask & ((1ull << lane) - 1));
+                edges[(int64_t)pos * r + a] = make_int2(b, __float_as_int(w));
+            }
+            c += __builtin_popcountll(mask);
+            while (mask) {                                        // fp32 sequential sum in edge order
+                const int src = __builtin_ctzll(mask);
+                mask &= mask - 1;
+                deg += readlane_f(w, src);
+            }
+        }
+        if (lane == 0) {
+            ecount[a] = c;
+            rinv[a] = 1.0f / sqrtf(deg + 1e-12f);
+        }
+    }
+    __syncthreads();
+
+    // S = w * (r_a * r_b) (the product of the two r is commutative: S is exactly symmetric, and with R = N it is
+    // mdx_knn_graph's S bit for bit); f = 0, r = p = y; y . y
+    const int kseed = (int)(kq < r ? kq : r);
+    int rc[TRD_ROWS];
+    float part = 0.0f;
+#pragma unroll
+    for (int u = 0; u < TRD_ROWS; ++u) {
+        const int a = t + u * TRD_THREADS;
+        rc[u] = 0;
+        if (a >= r) continue;
+        const int c = ecount[a];
+        rc[u] = c;
+        const float ra = rinv[a];
+        for (int e = 0; e < c; ++e) {
+            int2 ed = edges[(int64_t)e * r + a];
+            ed.y = __float_as_int(__int_as_float(ed.y) * (ra * rinv[ed.x]));
+            edges[(int64_t)e * r + a] = ed;
+        }
+        const float y = a < kseed && node[a] ? graph_weight(top_sims[q * r + a], gamma) : 0.0f;
+        fv[a] = 0.0f;
+        rv[a] = y;
+        pv[a] = y;
+        part = fmaf(y, y, part);
+    }
+    __syncthreads();                                              // node[] (apv) is read above: ap is written below
+    const float yy = trd_block_sum(part, red + TRD_WAVES);
+    float rr = yy;
+    int steps = 0;
+    bool active = yy > 0.0f && !(yy <= tol2 * yy);
+
+    // (c) CG: the recurrence and the stop rule of mdx_diffusion; a stopped query's later steps there change nothing
+    for (int64_t it = 0; it < iters && active; ++it) {
+        float dot = 0.0f;
+#pragma unroll
+        for (int u = 0; u < TRD_ROWS; ++u) {
+            const int a = t + u * TRD_THREADS;
+            if (a >= r) continue;
+            const int c = rc[u];
+            float acc = 0.0f;
+            for (int e0 = 0; e0 < c; e0 += TRD_GATHER) {
+                int2 ed[TRD_GATHER];
+#pragma unroll
+                for (int g = 0; g < TRD_GATHER; ++g)             // the batch's loads before any FMA
+                    ed[g] = e0 + g < c ? edges[(int64_t)(e0 + g) * r + a] : make_int2(0, 0);
+#pragma unroll
+                for (int g = 0; g < TRD_GATHER; ++g)             // edge order: the row's fixed fma chain
+                    if (e0 + g < c) acc = fmaf(__int_as_float(ed[g].y), pv[ed[g].x], acc);
+            }
+            const float p = pv[a], ap = fmaf(-alpha, acc, p);
+            apv[a] = ap;
+            dot = fmaf(p, ap, dot);
+        }
+        const float pap = trd_block_sum(dot, red);
+        if (!(pap > 0.0f && isfinite(pap))) break;                // A is SPD: p . Ap > 0 unless p == 0
+        const float step = rr / pap;
+        part = 0.0f;
+#pragma unroll
+        for (int u = 0; u < TRD_ROWS; ++u) {
+            const int a = t + u * TRD_THREADS;
+            if (a >= r) continue;
+            fv[a] = fmaf(step, pv[a], fv[a]);
+            const float x = fmaf(-step, apv[a], rv[a]);
+            rv[a] = x;
+            part = fmaf(x, x, part);
+        }
+        const float rrn = trd_block_sum(part, red + TRD_WAVES);
+        ++steps;
+        const float beta = rrn / rr;
+        rr = rrn;
+        if (rrn <= tol2 * yy) active = false;
+        if (active && it + 1 < iters) {
+#pragma unroll
+            for (int u = 0; u < TRD_ROWS; ++u) {
+                const int a = t + u * TRD_THREADS;
+                if (a < r) pv[a] = fmaf(beta, pv[a], rv[a]);
+            }
+            __syncthreads();                                      // the next SpMV reads every row's p
+        }
+    }
+
+    // (e) f of this thread's rows; the residual and the step count
+#pragma unroll
+    for (int u = 0; u < TRD_ROWS; ++u) {
+        const int a = t + u * TRD_THREADS;
+        if (a < r) F[a] = fv[a];
+    }
+    if (t == 0) {
+        if (residual) residual[q] = yy > 0.0f ? sqrtf(rr / yy) : 0.0f;
+        if (steps_out) steps_out[q] = steps;
+    }
+}
+
+// out[q, j] = scores[q, j] - 3, 4096 entries of one row per workgroup (VEC: 16-byte aligned rows, float4)
+template <bool VEC>
+__global__ __launch_bounds__(256) void diffusion_truncated_base_kernel(const float *scores, int64_t ld_scores, float *out,
+                                                                       int64_t ld_out, int64_t n, int64_t nblk)
+{
+    const int64_t q = blockIdx.x / nblk, j0 = (blockIdx.x - q * nblk) * (int64_t)4096;
+    const float *s = scores + q * ld_scores;
+    float *o = out + q * ld_out;
+    if (VEC) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            int64_t j = j0 + (u * 256 + threadIdx.x) * 4;
+            if (j + 4 <= n) {
+                float4 v = ld4(s + j);
+                v.x -= 3.0f; v.y -= 3.0f; v.z -= 3.0f; v.w -= 3.0f;
+                st4(o + j, v);
+            } else {
+                for (; j < n; ++j) o[j] = s[j] - 3.0f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int64_t j = j0 + u * 256 + threadIdx.x;
+            if (j < n) o[j] = s[j] - 3.0f;
+        }
+    }
+}
+
+// out[q, t_a] = f_a where f_a > 0 (a non-node keeps f = 0 and is never written)
+__global__ __launch_bounds__(256) void diffusion_truncated_scatter_kernel(const char *__restrict__ ws, int64_t k, int64_t r,
+                                                                          const int64_t *__restrict__ top_ids, int64_t n,
+                                                                          int64_t nq, float *out, int64_t ld_out)
+{
+    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= nq * r) return;
+    const int64_t q = x / r, a = x - q * r;
+    const float *F = (const float *)(ws + q * trd_query_bytes(k, r) + trd_edges_bytes(k, r) + trd_round(r * 4, 256));
+    const float f = F[a];
+    const int64_t id = top_ids[x];
+    if (f > 0.0f && id >= 0 && id < n) out[q * ld_out + id] = f;
+}
+
 static bool overlaps(const void *a, int64_t bytes_a, const void *b, int64_t bytes_b)
 {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -496,6 +780,89 @@ int mdx_diffusion(const int32_t *cols, const float *vals, const int32_t *counts,
     }
     hipLaunchKernelGGL(diffusion_final_kernel, dim3((unsigned)ceil_div(n, 64), (unsigned)ceil_div(nq, 64)), dim3(256), 0, s,
                        ws.F, n, nq, nqp, scores, ld_scores, out, ld_out, ws.st, residual, steps);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int mdx_knn_graph_weights(const int64_t *ids, const float *sims, int64_t n, int64_t k, float gamma, int32_t *cols, float *w,
+                          int32_t *counts, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    MDX_CHECK_ARG(ids && sims && cols && w && counts && workspace,
+                  "mdx_knn_graph_weights: NULL pointer (ids, sims, cols, w, counts and workspace are required)");
+    MDX_CHECK_ARG(n >= 1 && k >= 1, "mdx_knn_graph_weights: n=%lld k=%lld (each must be >= 1)", (long long)n, (long long)k);
+    MDX_CHECK_ARG(n < (1ll << 31), "mdx_knn_graph_weights: n=%lld must be < 2^31 (cols are int32)", (long long)n);
+    MDX_CHECK_ARG(k <= (1ll << 20), "mdx_knn_graph_weights: k=%lld too large", (long long)k);
+    MDX_CHECK_ARG(isfinite(gamma) && gamma >= 0.0f, "mdx_knn_graph_weights: gamma=%g must be finite and >= 0", (double)gamma);
+    const int64_t need = mdx_knn_graph_workspace(n);
+    if (workspace_bytes < need) {
+        set_error("mdx_knn_graph_weights: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    hipLaunchKernelGGL(knn_graph_edges_kernel, dim3((unsigned)ceil_div(n, DIF_WAVES)), dim3(64 * DIF_WAVES), 0,
+                       (hipStream_t)stream, ids, sims, n, k, gamma, cols, w, counts, (float *)workspace);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int64_t mdx_diffusion_truncated_workspace(int64_t n, int64_t k, int64_t nq, int64_t r)
+{
+    if (n < 1 || k < 1 || k > (1ll << 20) || nq < 1 || nq >= (1ll << 31) || r < 1 || r > MDX_DIFFUSION_MAX_R || r > n)
+        return 0;
+    return nq * trd_query_bytes(k, r);
+}
+
+int mdx_diffusion_truncated(const int32_t *cols, const float *w, const int32_t *counts, int64_t n, int64_t k,
+                            const float *scores, int64_t ld_scores, const int64_t *top_ids, const float *top_sims, int64_t nq,
+                            int64_t r, int64_t kq, float gamma, float alpha, int64_t iters, float tol, float *out,
+                            int64_t ld_out, float *residual, int32_t *steps, void *workspace, int64_t workspace_bytes,
+                            void *stream)
+{
+    MDX_CHECK_ARG(cols && w && counts && scores && top_ids && top_sims && out && workspace,
+                  "mdx_diffusion_truncated: NULL pointer (cols, w, counts, scores, top_ids, top_sims, out and workspace are "
+                  "required)");
+    MDX_CHECK_ARG(n >= 1 && k >= 1 && nq >= 1 && r >= 1 && kq >= 1,
+                  "mdx_diffusion_truncated: n=%lld k=%lld nq=%lld r=%lld kq=%lld (each must be >= 1)", (long long)n,
+                  (long long)k, (long long)nq, (long long)r, (long long)kq);
+    MDX_CHECK_ARG(r <= MDX_DIFFUSION_MAX_R && r <= n, "mdx_diffusion_truncated: r=%lld must be <= %d and <= n=%lld",
+                  (long long)r, MDX_DIFFUSION_MAX_R, (long long)n);
+    MDX_CHECK_ARG(n < (1ll << 31), "mdx_diffusion_truncated: n=%lld must be < 2^31 (cols are int32)", (long long)n);
+    MDX_CHECK_ARG(k <= (1ll << 20), "mdx_diffusion_truncated: k=%lld too large", (long long)k);
+    MDX_CHECK_ARG(nq * ceil_div(n, 4096) < (1ll << 31), "mdx_diffusion_truncated: nq=%lld too large for n=%lld (split the queries)",
+                  (long long)nq, (long long)n);
+    MDX_CHECK_ARG(ld_scores >= n && ld_out >= n, "mdx_diffusion_truncated: ld_scores=%lld ld_out=%lld must be >= n=%lld",
+                  (long long)ld_scores, (long long)ld_out, (long long)n);
+    MDX_CHECK_ARG(isfinite(gamma) && gamma >= 0.0f, "mdx_diffusion_truncated: gamma=%g must be finite and >= 0", (double)gamma);
+    MDX_CHECK_ARG(alpha >= 0.0f && alpha < 1.0f, "mdx_diffusion_truncated: alpha=%g must be in [0, 1)", (double)alpha);
+    MDX_CHECK_ARG(iters >= 1, "mdx_diffusion_truncated: iters=%lld must be >= 1", (long long)iters);
+    MDX_CHECK_ARG(isfinite(tol) && tol >= 0.0f, "mdx_diffusion_truncated: tol=%g must be finite and >= 0", (double)tol);
+    const int64_t span = ((nq - 1) * ld_out + n) * (int64_t)sizeof(float);
+    MDX_CHECK_ARG((out == scores && ld_out == ld_scores) ||
+                      !overlaps(out, span, scores, ((nq - 1) * ld_scores + n) * (int64_t)sizeof(float)),
+                  "mdx_diffusion_truncated: out overlaps scores (only out == scores with the same stride is allowed)");
+    const int64_t need = mdx_diffusion_truncated_workspace(n, k, nq, r);
+    if (workspace_bytes < need) {
+        set_error("mdx_diffusion_truncated: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    MDX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "mdx_diffusion_truncated: workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t lds = trd_lds(r);
+    auto solve = diffusion_truncated_solve_kernel;
+    MDX_HIP(hipFuncSetAttribute((const void *)solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)trd_lds(MDX_DIFFUSION_MAX_R)));
+    hipLaunchKernelGGL(solve, dim3((unsigned)nq), dim3(TRD_THREADS), (unsigned)lds, s, cols, w, counts, n, k, top_ids, top_sims,
+                       (int)r, kq, gamma, alpha, iters, tol * tol, (char *)workspace, residual, steps);
+    MDX_LAUNCH_CHECK();
+    const int64_t nblk = ceil_div(n, 4096);
+    const bool vec = (((uintptr_t)scores | (uintptr_t)out) & 15) == 0 && ld_scores % 4 == 0 && ld_out % 4 == 0;
+    if (vec)
+        hipLaunchKernelGGL(diffusion_truncated_base_kernel<true>, dim3((unsigned)(nq * nblk)), dim3(256), 0, s, scores, ld_scores,
+                           out, ld_out, n, nblk);
+    else
+        hipLaunchKernelGGL(diffusion_truncated_base_kernel<false>, dim3((unsigned)(nq * nblk)), dim3(256), 0, s, scores,
+                           ld_scores, out, ld_out, n, nblk);
+    MDX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(diffusion_truncated_scatter_kernel, dim3((unsigned)ceil_div(nq * r, 256)), dim3(256), 0, s,
+                       (const char *)workspace, k, r, top_ids, n, nq, out, ld_out);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }

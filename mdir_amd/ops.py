@@ -718,6 +718,94 @@ def diffusion(graph, scores, seed_ids, seed_sims, gamma, alpha, iters, tol, out=
     return (out, residual, steps) if return_residual else out
 
 
+def knn_graph_weights(ids, sims, gamma):
+    """The unnormalised affinity W of the diffusion graph (``mdx_knn_graph_weights``): ``(cols int32 [N, k], w fp32 [N, k],
+    counts int32 [N])``, cols and counts bit-identical to :func:`knn_graph`'s and ``w = max(s, 0) ** gamma`` before the
+    symmetric normalisation.  What :func:`diffusion_truncated` renormalises on each query's subgraph."""
+    gamma = _finite(gamma, "gamma")
+    ip = _dev(ids, torch.int64, "ids")
+    sp = _dev(sims, torch.float32, "sims")
+    if ids.dim() != 2 or tuple(sims.shape) != tuple(ids.shape):
+        raise ValueError("ids and sims must both be [N, k], got %s and %s" % (tuple(ids.shape), tuple(sims.shape)))
+    n, k = ids.shape
+    if n < 1 or k < 1:
+        raise ValueError("ids must be a non-empty [N, k], got %s" % (tuple(ids.shape),))
+    h = _lib.lib()
+    cols = torch.empty((n, k), dtype=torch.int32, device=ids.device)
+    w = torch.empty((n, k), dtype=torch.float32, device=ids.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    nbytes = h.mdx_knn_graph_workspace(n)
+    ws = _workspace(nbytes, ids.device)
+    with _on(ids):
+        check(h.mdx_knn_graph_weights(ip, sp, n, k, gamma, _vp(cols.data_ptr()), _vp(w.data_ptr()), _vp(counts.data_ptr()),
+                                      _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_knn_graph_weights")
+    return cols, w, counts
+
+
+DIFFUSION_MAX_R = 4096            # include/mdx.h MDX_DIFFUSION_MAX_R: the subgraph of a truncated solve lives in LDS
+DIFFUSION_TRUNCATED_WORKSPACE_CAP = 1 << 30     # bytes of per-query edge lists one truncated launch may hold
+
+
+def diffusion_truncated(graph, scores, top_ids, top_sims, kq, gamma, alpha, iters, tol, out=None, return_residual=False):
+    """Truncated diffusion scores ``[nq, N]`` (``mdx_diffusion_truncated``, the definition in ``include/mdx.h``): each query's
+    CG on the subgraph of its top-R first-stage rows, renormalised there; ``f`` where positive, else ``scores - 3``.
+    ``graph`` is ``(cols, w, counts)`` of :func:`knn_graph_weights` or an object with ``cols``, ``wvals`` and ``counts``;
+    ``top_ids`` int64 / ``top_sims`` fp32 ``[nq, R]`` (:func:`topk` of the scores with ``k = R``, ``R <= 4096``); the seeds
+    are their first ``min(kq, R)`` entries.  ``out`` may be ``scores`` (in place).  Queries run in groups whose workspace
+    stays under 1 GiB, which gives the same bits.  With ``return_residual``: ``(out, residual fp32 [nq], steps int32 [nq])``."""
+    cols, w, counts = graph if isinstance(graph, tuple) else (graph.cols, graph.wvals, graph.counts)
+    gamma = _finite(gamma, "gamma")
+    alpha = _finite(alpha, "alpha", 0.0, 1.0)
+    tol = _finite(tol, "tol")
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError("iters must be an integer >= 1, got %r" % (iters,))
+    if isinstance(kq, bool) or not isinstance(kq, int) or kq < 1:
+        raise ValueError("kq must be an integer >= 1, got %r" % (kq,))
+    if w is None:
+        raise ValueError("graph has no unnormalised weights (build it with weights=True)")
+    _dev(cols, torch.int32, "cols")
+    _dev(w, torch.float32, "w")
+    _dev(counts, torch.int32, "counts")
+    if cols.dim() != 2 or tuple(w.shape) != tuple(cols.shape) or tuple(counts.shape) != (cols.shape[0],):
+        raise ValueError("graph: cols / w [N, k] and counts [N] expected, got %s, %s, %s"
+                         % (tuple(cols.shape), tuple(w.shape), tuple(counts.shape)))
+    n, k = cols.shape
+    sp, ld = _rows(scores, "scores")
+    nq = scores.shape[0]
+    if scores.shape[1] != n:
+        raise ValueError("scores must be [nq, %d], got %s" % (n, tuple(scores.shape)))
+    _dev(top_ids, torch.int64, "top_ids")
+    _dev(top_sims, torch.float32, "top_sims")
+    if top_ids.dim() != 2 or tuple(top_sims.shape) != tuple(top_ids.shape) or top_ids.shape[0] != nq:
+        raise ValueError("top_ids and top_sims must both be [%d, R], got %s and %s"
+                         % (nq, tuple(top_ids.shape), tuple(top_sims.shape)))
+    r = top_ids.shape[1]
+    if not 1 <= r <= min(n, DIFFUSION_MAX_R):
+        raise ValueError("R = %d must be in [1, min(N, %d)]" % (r, DIFFUSION_MAX_R))
+    if out is None:
+        out = torch.empty((nq, n), dtype=torch.float32, device=scores.device)
+    elif tuple(out.shape) != (nq, n):
+        raise ValueError("out must be [%d,%d]" % (nq, n))
+    _, ld_out = _rows(out, "out")
+    residual = torch.empty((nq,), dtype=torch.float32, device=scores.device) if return_residual else None
+    steps = torch.empty((nq,), dtype=torch.int32, device=scores.device) if return_residual else None
+    h = _lib.lib()
+    group = max(1, min(nq, DIFFUSION_TRUNCATED_WORKSPACE_CAP // h.mdx_diffusion_truncated_workspace(n, k, 1, r)))
+    nbytes = h.mdx_diffusion_truncated_workspace(n, k, group, r)
+    ws = _workspace(nbytes, scores.device)
+    with _on(scores):
+        for q0 in range(0, nq, group):
+            q1 = min(nq, q0 + group)
+            check(h.mdx_diffusion_truncated(_vp(cols.data_ptr()), _vp(w.data_ptr()), _vp(counts.data_ptr()), n, k,
+                                            _vp(scores[q0].data_ptr()), ld, _vp(top_ids[q0].data_ptr()),
+                                            _vp(top_sims[q0].data_ptr()), q1 - q0, r, kq, gamma, alpha, iters, tol,
+                                            _vp(out[q0].data_ptr()), ld_out,
+                                            _vp(residual[q0].data_ptr()) if return_residual else None,
+                                            _vp(steps[q0].data_ptr()) if return_residual else None, _vp(ws.data_ptr()),
+                                            ws.numel(), _stream()), "mdx_diffusion_truncated")
+    return (out, residual, steps) if return_residual else out
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)

@@ -129,9 +129,11 @@ class DiffusionGraph:
     (:func:`dba_chunk`), then the graph kernel on the whole ``[N, k]`` lists.  The lists do not depend on the chunk.
 
     Attributes: ``cols`` int32 / ``vals`` fp32 ``[N, k]``, ``counts`` int32 ``[N]``, ``n``, ``k`` (``min(k, N)``),
-    ``gamma``.  ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy."""
+    ``gamma``, and ``wvals`` fp32 ``[N, k]``: with ``weights=True`` the unnormalised weights that the truncated solve
+    renormalises on each query's subgraph (``mdx_knn_graph_weights``, N * k * 4 more bytes), else None.
+    ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy."""
 
-    def __init__(self, vecs, k=50, gamma=3.0, chunk=None, layout="ND"):
+    def __init__(self, vecs, k=50, gamma=3.0, chunk=None, layout="ND", weights=False):
         _check_int(k, "k")
         _check_real(gamma, "gamma")
         if chunk is not None:
@@ -162,6 +164,7 @@ class DiffusionGraph:
                 index.close()
         del scores, workspace
         self.cols, self.vals, self.counts = ops.knn_graph(ids, sims, gamma)
+        self.wvals = ops.knn_graph_weights(ids, sims, gamma)[1] if weights else None     # same cols / counts
         self.n, self.k, self.gamma = n, k, float(gamma)
 
     def edges(self):
@@ -169,11 +172,11 @@ class DiffusionGraph:
         return int(self.counts.sum(dtype=torch.int64).item())
 
     def close(self):
-        self.cols = self.vals = self.counts = None
+        self.cols = self.vals = self.counts = self.wvals = None
 
 
 def diffusion(qvecs, vecs, graph=None, kq=10, alpha=0.99, iters=20, tol=1e-6, index=None, compute="chain", scores=None,
-              return_residual=False):
+              return_residual=False, truncate=None):
     """Diffusion scores ``[Q, N]`` of the queries ``qvecs`` ``[Q, D]`` on the database ``vecs`` ``[N, D]``
     (``mdx_diffusion``; definition in ``include/mdx.h``): seeds ``max(s, 0) ** gamma`` at the ``min(kq, N)`` best
     first-stage scores, CG on ``(I - alpha S) f = y`` for at most ``iters`` steps, then ``f`` where positive and the
@@ -182,16 +185,27 @@ def diffusion(qvecs, vecs, graph=None, kq=10, alpha=0.99, iters=20, tol=1e-6, in
     ``graph`` is a :class:`DiffusionGraph` of ``vecs`` (built here with its defaults when None; pass one to reuse it across
     batches); its ``gamma`` also weights the seeds.  The first-stage scores come from ``scores`` when given (never
     written), else from the similarity of ``vecs`` or ``index`` in mode ``compute`` (as :func:`query_expansion`).
-    With ``return_residual``: ``(scores, residual [Q], steps [Q])``, the final ``||r|| / ||y||`` and the steps taken."""
+    With ``return_residual``: ``(scores, residual [Q], steps [Q])``, the final ``||r|| / ||y||`` and the steps taken.
+
+    ``truncate`` (an integer, ``kq <= truncate <= 4096``) solves each query on the subgraph of its ``R = min(truncate, N)``
+    best first-stage rows instead (``mdx_diffusion_truncated``): the graph must hold ``wvals`` (``weights=True``; built so
+    when None).  None: the full solve."""
     _check_int(kq, "kq")
     _check_real(alpha, "alpha", upper=1.0)
     _check_int(iters, "iters")
     _check_real(tol, "tol")
+    if truncate is not None:
+        _check_int(truncate, "truncate")
+        if truncate > ops.DIFFUSION_MAX_R or truncate < kq:
+            raise ValueError("truncate must be in [kq, %d] = [%d, %d], got %r" % (ops.DIFFUSION_MAX_R, kq, ops.DIFFUSION_MAX_R,
+                                                                                   truncate))
+        if graph is not None and getattr(graph, "wvals", None) is None:
+            raise ValueError("truncate needs the graph's unnormalised weights: build it with DiffusionGraph(..., weights=True)")
     if vecs.dim() != 2 or qvecs.dim() != 2 or qvecs.shape[1] != vecs.shape[1]:
         raise ValueError("qvecs [Q, D] and vecs [N, D] expected, got %s and %s" % (tuple(qvecs.shape), tuple(vecs.shape)))
     n = vecs.shape[0]
     if graph is None:
-        graph = DiffusionGraph(vecs)
+        graph = DiffusionGraph(vecs, weights=truncate is not None)
     if graph.n != n:
         raise ValueError("graph has %d rows, the database %d" % (graph.n, n))
     if scores is None:
@@ -201,6 +215,10 @@ def diffusion(qvecs, vecs, graph=None, kq=10, alpha=0.99, iters=20, tol=1e-6, in
         if tuple(scores.shape) != (qvecs.shape[0], n):
             raise ValueError("scores must be [%d, %d], got %s" % (qvecs.shape[0], n, tuple(scores.shape)))
         first, out = scores, None
+    if truncate is not None:
+        top_ids, top_sims = ops.topk(first, min(truncate, n))       # the seeds are its first min(kq, R) entries
+        return ops.diffusion_truncated(graph, first, top_ids, top_sims, kq, graph.gamma, alpha, iters, tol, out=out,
+                                       return_residual=return_residual)
     seed_ids, seed_sims = ops.topk(first, min(kq, n))
     return ops.diffusion(graph, first, seed_ids, seed_sims, graph.gamma, alpha, iters, tol, out=out,
                          return_residual=return_residual)

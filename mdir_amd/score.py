@@ -22,7 +22,8 @@ not in the reference) add the re-ranking every table on the revisited protocol r
 the queries and DBA of the database (``mdir_amd/rerank.py``); with both, DBA runs first and alpha-QE searches the augmented
 database.  Single-process only for now.  ``diffusion: {k, kq, gamma, alpha, iters, tol}`` (criterion key, every
 sub-key optional, defaults of the paper's release) re-ranks by diffusion on a mutual kNN graph of the database
-(``rerank.diffusion``), after DBA when both are set; not together with query_expansion; single-process only.
+(``rerank.diffusion``), after DBA when both are set; not together with query_expansion; single-process only.  The optional
+sub-key ``truncate: R`` (``kq <= R <= 4096``; no default) solves each query on the subgraph of its top-R rows instead.
 """
 import gzip
 import json
@@ -178,9 +179,10 @@ class CirDatasetAp:
             if self.diffusion:
                 p = self.diffusion
                 with range_("diffusion"):
-                    graph = rerank.DiffusionGraph(vecs, k=p["k"], gamma=p["gamma"])
+                    truncate = p.get("truncate")
+                    graph = rerank.DiffusionGraph(vecs, k=p["k"], gamma=p["gamma"], weights=truncate is not None)
                     scores = rerank.diffusion(qvecs, vecs, graph, kq=p["kq"], alpha=p["alpha"], iters=p["iters"],
-                                              tol=p["tol"], scores=scores)
+                                              tol=p["tol"], scores=scores, truncate=truncate)
                     graph.close()
             if self.ranking == "full":
                 with range_("ranking"):
@@ -220,14 +222,16 @@ def _rerank_params(value, key):
 
 def _diffusion_params(value):
     """``{k, kq, gamma, alpha, iters, tol}`` of the ``diffusion`` criterion key, each optional (the defaults of
-    ``rerank.DIFFUSION_DEFAULTS``), validated (None: the key is absent)."""
+    ``rerank.DIFFUSION_DEFAULTS``), and ``truncate``, optional without a default (in the result only when given),
+    validated (None: the key is absent)."""
     if value is None:
         return None
     if not isinstance(value, dict):
-        raise ValueError("diffusion: a mapping with the optional keys k, kq, gamma, alpha, iters, tol, got %r" % (value,))
-    unknown = set(value) - set(rerank.DIFFUSION_DEFAULTS)
+        raise ValueError("diffusion: a mapping with the optional keys k, kq, gamma, alpha, iters, tol, truncate, got %r"
+                         % (value,))
+    unknown = set(value) - set(rerank.DIFFUSION_DEFAULTS) - {"truncate"}
     if unknown:
-        raise ValueError("diffusion: unknown keys %s (allowed: k, kq, gamma, alpha, iters, tol)" % sorted(unknown))
+        raise ValueError("diffusion: unknown keys %s (allowed: k, kq, gamma, alpha, iters, tol, truncate)" % sorted(unknown))
     out = dict(rerank.DIFFUSION_DEFAULTS, **value)
     for key in ("k", "kq", "iters"):
         x = out[key]
@@ -240,6 +244,11 @@ def _diffusion_params(value):
             raise ValueError("diffusion: %s must be a finite number >= 0%s, got %r"
                              % (key, "" if upper is None else " and < %g" % upper, x))
         out[key] = float(x)
+    if "truncate" in out:
+        x = out["truncate"]
+        if isinstance(x, bool) or not isinstance(x, int) or not out["kq"] <= x <= ops.DIFFUSION_MAX_R:
+            raise ValueError("diffusion: truncate must be an integer in [kq, %d] = [%d, %d], got %r"
+                             % (ops.DIFFUSION_MAX_R, out["kq"], ops.DIFFUSION_MAX_R, x))
     return out
 
 
