@@ -61,7 +61,35 @@ typedef enum mdx_layout {
  * stores descriptors (and the queries of a call) as IEEE fp16 and multiplies them on the
  * fp16 MFMA with fp32 accumulation (BASELINE.json configs[4]); scores then carry fp16 input
  * rounding (~1e-3 relative) -- a separate, looser parity contract (tests/test_gpu_f16.py). */
-typedef enum mdx_storage { MDX_F32 = 0, MDX_F16 = 1 } mdx_storage;
+/* MDX_I8 stores every row as int8 codes with one fp32 scale per row (a quarter of the fp32 bytes) and multiplies the codes
+ * on the int8 MFMA (v_mfma_i32_16x16x64_i8), whose int32 accumulation is exact -- so, unlike fp16, every score is defined
+ * to the bit:
+ *
+ *   Quantising one fp32 row x of length d (a query row is x = q - center, one fp32 subtraction, when a center is given).
+ *   Every operation is IEEE fp32 with round-to-nearest-even; nothing is contracted into an fma:
+ *     a = max_k |x_k|                                       (exact)
+ *     a == 0:  scale = 0, every code 0
+ *     else:    inv   = 127.0f / a                           (correctly rounded division)
+ *              c_k   = clamp(rint(x_k * inv), -127, 127)    (one rounded product; rint: half to even)
+ *              scale = a / 127.0f                           (correctly rounded division)
+ *   Score of query q against row i:
+ *     acc          = sum_k c_q,k * c_i,k                    (int32, exact: |acc| <= 127^2 d_pad < 2^31)
+ *     scores[q, i] = (float)acc * (scale_i * scale_q)       (two rounded products; (float) rounds to nearest even)
+ *   Zero padding of k adds nothing, so neither the padding nor the order of the k terms can change a bit.  d is refused
+ *   (MDX_ERR_INVALID) where 127^2 * round_up(d, 64) could reach 2^31, i.e. d > 133 120.  Rows (or queries) holding a NaN or
+ *   an infinity, or whose a is below 2^-100, carry no contract.
+ *
+ *   Error bound against the unquantised dot product.  With u = 2^-24, inv = (127/a)(1+d1), fl(x_k inv) = x_k inv (1+d2) and
+ *   scale = (a/127)(1+d3), |d_i| <= u: |fl(x_k inv)| <= 127 (1+u)^2 < 127.5, so the clamp never acts and |c_k - fl(x_k inv)|
+ *   <= 1/2; scale fl(x_k inv) = x_k (1+d1)(1+d2)(1+d3), so e_x = x - scale c_x obeys
+ *     ||e_x||_inf <= scale/2 + a ((1+u)^3 - 1) <= scale/2 + 127 scale ((1+u)^3 - 1) / (1-u) <= scale (1/2 + 2^-15) =: E_x.
+ *   x.q - (scale_x c_x).(scale_q c_q) = e_x.q + scale_x c_x.e_q, and the score is that exact product of the quantised rows
+ *   times (1+d4)(1+d5)(1+d6) (three roundings: (float)acc, the scale product, the final product), so, barring underflow of
+ *   scale_i * scale_q,
+ *     |x.q - s| <= E_x ||q||_1 + scale_x ||c_x||_1 E_q + 2^-22 |s|
+ *   for every pair -- each term is computable from the inputs, the codes and the scales (tests/test_gpu_i8.py evaluates it).
+ *   mdx_quantize_i8 returns the codes and scales of this definition. */
+typedef enum mdx_storage { MDX_F32 = 0, MDX_F16 = 1, MDX_I8 = 2 } mdx_storage;
 
 typedef enum mdx_pool_kind { MDX_POOL_GEM = 0, MDX_POOL_MAC = 1, MDX_POOL_SPOC = 2 } mdx_pool_kind;
 
@@ -255,7 +283,7 @@ typedef struct mdx_index mdx_index;
  * Allocates n_pad*d_pad*4 bytes of device memory.  An fp32 shard's creation waits for
  * the build on `stream` (the shard's largest magnitude -- the block exponent of
  * MDX_F32_SPLIT2 -- is reduced inside the re-tiling pass and read back here, once);
- * an fp16 shard's only if the build fails. */
+ * an fp16 or int8 shard's only if the build fails. */
 int mdx_index_create(mdx_index **out, const float *src, int64_t n, int64_t d, int layout,
                      int64_t row_offset, void *stream);
 /* Same with an explicit storage type (mdx_storage).  `src` is fp32 in both cases. */
@@ -266,6 +294,10 @@ int mdx_index_create_ex(mdx_index **out, const float *src, int64_t n, int64_t d,
  * ~190 ms per create / destroy pair -- seventy times the re-tiling itself; a host that builds an index per evaluation hands
  * in memory from its own pool (PyTorch's caching allocator in mdir_amd/ops.py). */
 int64_t mdx_index_bytes(int64_t n, int64_t d, int storage);
+/*   With RT = round_up(ceil(n / 16), 8) row tiles and d_pad = round_up(d, 64):
+ *     MDX_F32: RT * 16 * d_pad * 4 + 256     MDX_F16: RT * 16 * d_pad * 2 + 256
+ *     MDX_I8:  RT * 16 * d_pad + RT * 16 * 4 + 256   (codes in tiles of 16 rows x 64 k, then one fp32 scale per padded row)
+ *   0 for n <= 0, d <= 0, an unknown storage or (MDX_I8) d > 133 120. */
 int mdx_index_create_in(mdx_index **out, const float *src, int64_t n, int64_t d, int layout, int64_t row_offset,
                         int storage, void *memory, int64_t memory_bytes, void *stream);
 int mdx_index_destroy(mdx_index *index);
@@ -273,8 +305,15 @@ int mdx_index_destroy(mdx_index *index);
 int mdx_index_info(const mdx_index *index, int64_t *n, int64_t *d, int64_t *row_offset,
                    int64_t *device_bytes);
 
-/* Bytes of scratch mdx_scores needs for nq queries of dimension d. */
+/* Bytes of scratch mdx_scores needs for nq queries of dimension d (the fp32 query tiles; an fp16 shard uses half of it, an
+ * int8 shard round_up(nq, 16) * (round_up(d, 64) + 4) bytes of it: the int8 query tiles and one scale per padded query). */
 int64_t mdx_scores_workspace(int64_t nq, int64_t d);
+
+/* The int8 quantisation of MDX_I8 (see mdx_storage) of n rows of dimension d, `src` in `layout` (device, fp32):
+ *   codes [n, d] int8 row-major, scales [n] fp32 -- the values an MDX_I8 index holds for the same rows (the same device
+ * functions quantise both; e.g. to keep a quantised database on disk).  Enqueue only.  MDX_ERR_INVALID for NULL pointers,
+ * n <= 0, d <= 0, d > 133 120 or an unknown layout. */
+int mdx_quantize_i8(const float *src, int64_t n, int64_t d, int layout, int8_t *codes, float *scales, void *stream);
 
 /* Similarity of nq queries against every row of the shard:
  *   scores[q, i] = sum_k queries(q,k) * db(i,k)      scores row-major [nq, n]
@@ -327,7 +366,8 @@ int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *quer
 typedef enum mdx_compute { MDX_F32_CHAIN = 0, MDX_F32_SPLIT3 = 1, MDX_F32_SPLIT2 = 2 } mdx_compute;
 
 /* mdx_scores with an explicit compute mode; workspace of at least mdx_scores_workspace_ex(nq, d, compute) bytes
- * (MDX_F32_SPLIT3: 6 bytes per padded query element; MDX_F32_SPLIT2: 4 + 256 bytes).  Both need an MDX_F32 shard. */
+ * (MDX_F32_SPLIT3: 6 bytes per padded query element; MDX_F32_SPLIT2: 4 + 256 bytes).  Both need an MDX_F32 shard (an fp16 or
+ * int8 one is refused with MDX_ERR_INVALID). */
 int64_t mdx_scores_workspace_ex(int64_t nq, int64_t d, int compute);
 int mdx_scores_ex(const mdx_index *index, const float *queries, int64_t nq, int qlayout, const float *center,
                   float *scores, void *workspace, int64_t workspace_bytes, int compute, void *stream);
@@ -603,7 +643,7 @@ int mdx_exchange_scores(mdx_comm *comm, const float *local, int64_t nq, const in
  *   every step:        mdx_scores_p2p(index, queries, nq, ..., p, ...)  once per shard (or row chunk) this rank holds
  *                      mdx_p2p_close_step(p, &mine, stream)             mine = this rank's queries x all rows, valid until the
  *                                                                       step after next is opened by any peer
- * Every rank must run the same steps with the same nq.  nq <= 128; fp32 shards; the shard's first global row is the index's
+ * Every rank must run the same steps with the same nq.  nq <= 128; fp32 shards (fp16 and int8 ones are refused); the shard's first global row is the index's
  * row_offset.  HARDWARE STATUS: exercised with several rank processes on ONE GPU (same-device IPC); it has not run over xGMI --
  * tools/preflight_ranks.py checks it on a multi-GPU node before bench.py uses it, and mdx_exchange_scores stays the default.
  * Needs HSA_ENABLE_IPC_MODE_LEGACY=0 (dmabuf IPC) in the environment of every rank process. */

@@ -17,6 +17,7 @@
 #include "mdx_scores_kernel.h"
 #include "mdx_scores_split_kernel.h"
 #include "mdx_scores_stream_kernel.h"
+#include "mdx_scores_i8_kernel.h"
 
 namespace mdx {
 
@@ -136,6 +137,104 @@ __global__ __launch_bounds__(256) void retile_block_kernel(const float *__restri
     }
 }
 
+// ---------------------------------------------------------------------------
+// The int8 form of the re-tiling (MDX_I8, include/mdx.h states the quantisation).  A row's codes need its absmax first, so it
+// takes three launches: i8_absmax_kernel (a = max_k |x_k| per row, into the scale array), retile_i8_kernel (codes, reading a)
+// and i8_scale_kernel (a -> a / 127 in place).  mdx_quantize_i8 is the same three steps with row-major codes out.
+//   int8 tile = 16 rows x 64 k: lane (g, j), byte e = (row j, k 64 kb + 16 g + e)
+// ---------------------------------------------------------------------------
+constexpr int64_t I8_MAX_DPAD = 133120;        // largest multiple of 64 with 127^2 * d_pad < 2^31 (exact int32 accumulation)
+
+__device__ __forceinline__ float i8_inv(float a) { return __fdiv_rn(127.0f, a); }
+__device__ __forceinline__ float i8_scale(float a) { return __fdiv_rn(a, 127.0f); }
+__device__ __forceinline__ uint32_t i8_code(float x, float a, float inv)      // the code's byte
+{
+    if (a == 0.f) return 0u;
+    const float y = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.f), 127.f);
+    return (uint32_t)(uint8_t)(int8_t)(int)y;
+}
+// element (row, k) of the source, center[k] subtracted
+template <bool ROWMAJOR>
+__device__ __forceinline__ float i8_src(const float *src, int64_t n, int64_t d, const float *center, int64_t row, int64_t k)
+{
+    const float x = ROWMAJOR ? src[row * d + k] : src[k * n + row];
+    return center ? x - center[k] : x;
+}
+
+// a of rows 0 .. rows_pad-1 (0 for rows >= n).  Row-major: a wave per row; dimension-major: a thread per row (coalesced along rows)
+template <bool ROWMAJOR>
+__global__ __launch_bounds__(256) void i8_absmax_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ center,
+                                                        float *__restrict__ amax, int64_t rows_pad)
+{
+    if constexpr (ROWMAJOR) {
+        const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+        const int lane = threadIdx.x & 63;
+        if (row >= rows_pad) return;
+        float m = 0.f;
+        if (row < n)
+            for (int64_t k = lane; k < d; k += 64) m = fmaxf(m, fabsf(i8_src<true>(src, n, d, center, row, k)));
+        m = wave_max(m);
+        if (lane == 0) amax[row] = m;
+    } else {
+        const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (row >= rows_pad) return;
+        float m = 0.f;
+        if (row < n)
+            for (int64_t k = 0; k < d; ++k) m = fmaxf(m, fabsf(i8_src<false>(src, n, d, center, row, k)));
+        amax[row] = m;
+    }
+}
+
+// one wave per tile (rt, kb) of RT x KB; every lane assembles its 16 bytes
+template <bool ROWMAJOR>
+__global__ __launch_bounds__(256) void retile_i8_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ center,
+                                                        const float *__restrict__ amax, i32x4 *__restrict__ tiles, int64_t RT, int64_t KB)
+{
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= RT * KB) return;
+    const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+    const int64_t row = (tile / KB) * TILE_ROWS + j, k0 = (tile % KB) * 64 + 16 * g;
+    i32x4 w = {0, 0, 0, 0};
+    if (row < n) {
+        const float a = amax[row], inv = i8_inv(a);
+        float x[16];
+        if (ROWMAJOR && !center && k0 + 16 <= d) {
+            const f32x4u *p = (const f32x4u *)(src + row * d + k0);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const f32x4u t = p[v];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[4 * v + e] = t[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) x[e] = k0 + e < d ? i8_src<ROWMAJOR>(src, n, d, center, row, k0 + e) : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) w[e >> 2] |= (int)(i8_code(x[e], a, inv) << (8 * (e & 3)));
+    }
+    tiles[tile * 64 + lane] = w;
+}
+
+__global__ __launch_bounds__(256) void i8_scale_kernel(float *__restrict__ amax, int64_t rows)
+{
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row < rows) amax[row] = i8_scale(amax[row]);
+}
+
+// mdx_quantize_i8: codes [n, d] row-major, one byte per thread (consecutive threads: consecutive k of a row)
+template <bool ROWMAJOR>
+__global__ __launch_bounds__(256) void quantize_i8_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ amax,
+                                                          int8_t *__restrict__ codes)
+{
+    const int64_t total = n * d;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t row = e / d, k = e % d;
+        const float a = amax[row];
+        codes[e] = (int8_t)(uint8_t)i8_code(i8_src<ROWMAJOR>(src, n, d, nullptr, row, k), a, i8_inv(a));
+    }
+}
+
 // Loader/consumer kernel (4 MFMA waves + 4 LDS-DMA loader waves), chunks of 2 tiles along k,
 // ring of 3 stages.  R = 2 row tiles per consumer (128-row workgroups, (QT+8)*6 KiB of LDS)
 // for shards of >= 32 768 rows; R = 1 (64-row workgroups) below, so that small shards still
@@ -225,6 +324,45 @@ static int launch_f16_stream(const f32x4 *db, const f32x4 *qt, float *out, int64
     const int64_t blocks = ceil_div(RT, (int64_t)STREAM_CW * R);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(STREAM_CW * 64), lds, s, db, qt, out, n, KB, nq_valid);
     return MDX_OK;
+}
+
+template <int QT, int R>
+static int launch_i8_stream(const f32x4 *db, const float *db_scale, const f32x4 *qt, const float *q_scale, float *out, int64_t n, int64_t RT,
+                            int KB, int nq_valid, hipStream_t s, int passes)
+{
+    constexpr int WGS = QT <= 5 ? 3 : 2;
+    auto kern = scores_i8_stream_kernel<QT, R, WGS>;
+    constexpr int lds = stream_lds_bytes<QT, R>();
+    static bool opted[64];
+    int rc = lds_opt_in((const void *)kern, lds, opted);
+    if (rc != MDX_OK) return rc;
+    const int64_t blocks = ceil_div(RT, (int64_t)STREAM_CW * R);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(STREAM_CW * 64), lds, s, db, db_scale, qt, q_scale, out, n, KB,
+                       nq_valid);
+    return MDX_OK;
+}
+
+template <int QT>
+static int launch_i8_qt(bool r2, const f32x4 *db, const float *db_scale, const f32x4 *qt, const float *q_scale, float *out, int64_t n,
+                        int64_t RT, int KB, int nq_valid, hipStream_t s, int passes)
+{
+    return r2 ? launch_i8_stream<QT, 2>(db, db_scale, qt, q_scale, out, n, RT, KB, nq_valid, s, passes)
+              : launch_i8_stream<QT, 1>(db, db_scale, qt, q_scale, out, n, RT, KB, nq_valid, s, passes);
+}
+
+static int dispatch_i8(int qt, bool r2, const f32x4 *db, const float *db_scale, const f32x4 *q, const float *q_scale, float *out, int64_t n,
+                       int64_t RT, int KB, int nq_valid, hipStream_t s, int passes)
+{
+    switch (qt) {
+        case 1: return launch_i8_qt<1>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 2: return launch_i8_qt<2>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 3: return launch_i8_qt<3>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 4: return launch_i8_qt<4>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 5: return launch_i8_qt<5>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 6: return launch_i8_qt<6>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        case 7: return launch_i8_qt<7>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+        default: return launch_i8_qt<8>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
+    }
 }
 
 // mode bit0: R = 2 (else 1), bit1: fp16 shard
@@ -374,7 +512,8 @@ struct mdx_index {
     f32x4 *tiles;
     int64_t n, d, d_pad, RT, RT_pad, KB, row_offset;
     int64_t bytes;
-    int storage;        // MDX_F32 / MDX_F16
+    int storage;        // MDX_F32 / MDX_F16 / MDX_I8
+    float *scales;      // MDX_I8: one scale per padded row, behind the tiles (nullptr otherwise)
     bool owns;          // tiles came from hipMalloc here (mdx_index_create*) and are freed on destroy; false: the caller's memory
     uint32_t max_bits;  // fp32 shards: bit pattern of the largest finite |x| (read back once at creation): the scale of MDX_F32_SPLIT2
 };
@@ -398,10 +537,33 @@ int mdx_capture_recover(void *stream)
 }
 const char *mdx_last_error(void) { return mdx::g_err; }
 
+// MDX_I8: tiles of 16 rows x 64 k (KB of them per row tile) and the scales of the RT * 16 rows, in three launches
+static int retile_i8(const float *src, int64_t n, int64_t d, bool rowmajor, const float *center, f32x4 *tiles, int64_t RT, int64_t KB,
+                     float *scales, hipStream_t s)
+{
+    const int64_t rows = RT * TILE_ROWS;
+    MDX_CHECK_ARG(ceil_div(RT * KB, (int64_t)4) < (1ll << 31) && ceil_div(rows, (int64_t)4) < (1ll << 31), "matrix too large to re-tile in one launch");
+    const dim3 block(256), grid_abs((unsigned)(rowmajor ? ceil_div(rows, (int64_t)4) : ceil_div(rows, (int64_t)256)));
+    const dim3 grid_tiles((unsigned)ceil_div(RT * KB, (int64_t)4)), grid_rows((unsigned)ceil_div(rows, (int64_t)256));
+    i32x4 *t = (i32x4 *)tiles;
+    if (rowmajor) {
+        hipLaunchKernelGGL(i8_absmax_kernel<true>, grid_abs, block, 0, s, src, n, d, center, scales, rows);
+        hipLaunchKernelGGL(retile_i8_kernel<true>, grid_tiles, block, 0, s, src, n, d, center, (const float *)scales, t, RT, KB);
+    } else {
+        hipLaunchKernelGGL(i8_absmax_kernel<false>, grid_abs, block, 0, s, src, n, d, center, scales, rows);
+        hipLaunchKernelGGL(retile_i8_kernel<false>, grid_tiles, block, 0, s, src, n, d, center, (const float *)scales, t, RT, KB);
+    }
+    hipLaunchKernelGGL(i8_scale_kernel, grid_rows, block, 0, s, scales, rows);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
 static int retile(const float *src, int64_t n, int64_t d, int layout, const float *center,
-                  f32x4 *tiles, int64_t RT, int64_t KB, hipStream_t s, int storage = MDX_F32, uint32_t *absmax = nullptr)
+                  f32x4 *tiles, int64_t RT, int64_t KB, hipStream_t s, int storage = MDX_F32, uint32_t *absmax = nullptr,
+                  float *scales = nullptr)
 {
     const bool rowmajor = layout != MDX_DIM_MAJOR, f16 = storage == MDX_F16;
+    if (storage == MDX_I8) return retile_i8(src, n, d, rowmajor, center, tiles, RT, KB, scales, s);
     // blocks: 16 rows x 256 k (row-major) or 32 k x 256 rows (dimension-major: two fp32 k blocks or one fp16 k block)
     const int64_t gx = rowmajor ? RT : ceil_div(RT, (int64_t)16);
     const int64_t gy = rowmajor ? ceil_div(KB * (f16 ? 32 : 16), (int64_t)256) : (f16 ? KB : ceil_div(KB, (int64_t)2));
@@ -427,18 +589,20 @@ static void index_geometry(mdx_index *ix, int64_t n, int64_t d, int storage)
     ix->n = n;
     ix->d = d;
     ix->storage = storage;
-    ix->d_pad = round_up(d, 64);                                  // 4 fp32 or 2 fp16 k-blocks
-    ix->KB = ix->d_pad / (storage == MDX_F16 ? 32 : TILE_K);
+    ix->d_pad = round_up(d, 64);                                  // 4 fp32, 2 fp16 or 1 int8 k-blocks
+    ix->KB = ix->d_pad / (storage == MDX_F16 ? 32 : storage == MDX_I8 ? 64 : TILE_K);
     ix->RT = ceil_div(n, TILE_ROWS);
     // every wave of every workgroup has a tile to read: 8 row tiles per workgroup, 16 for the split-precision kernel (fp32 shards)
     ix->RT_pad = round_up(ix->RT, storage == MDX_F32 ? 16 : 8);
-    ix->bytes = ix->RT_pad * ix->KB * 1024;
+    ix->bytes = ix->RT_pad * ix->KB * 1024 + (storage == MDX_I8 ? ix->RT_pad * TILE_ROWS * 4 : 0);    // int8: + the row scales
     ix->max_bits = 0;
+    ix->scales = nullptr;
 }
 
 int64_t mdx_index_bytes(int64_t n, int64_t d, int storage)
 {
-    if (n <= 0 || d <= 0 || (storage != MDX_F32 && storage != MDX_F16)) return 0;
+    if (n <= 0 || d <= 0 || (storage != MDX_F32 && storage != MDX_F16 && storage != MDX_I8)) return 0;
+    if (storage == MDX_I8 && round_up(d, 64) > I8_MAX_DPAD) return 0;
     mdx_index g;
     index_geometry(&g, n, d, storage);
     return g.bytes + 256;                                          // + one word behind the tiles: the |x| maximum
@@ -454,9 +618,12 @@ int mdx_index_create_in(mdx_index **out, const float *src, int64_t n, int64_t d,
                         void *memory, int64_t memory_bytes, void *stream)
 {
     MDX_CHECK_ARG(out && src, "mdx_index_create: NULL pointer");
-    MDX_CHECK_ARG(storage == MDX_F32 || storage == MDX_F16, "mdx_index_create: storage %d", storage);
+    MDX_CHECK_ARG(storage == MDX_F32 || storage == MDX_F16 || storage == MDX_I8, "mdx_index_create: storage %d", storage);
     MDX_CHECK_ARG(n > 0 && d > 0, "mdx_index_create: n=%lld d=%lld must be positive",
                   (long long)n, (long long)d);
+    MDX_CHECK_ARG(storage != MDX_I8 || round_up(d, 64) <= I8_MAX_DPAD,
+                  "mdx_index_create: d=%lld too large for an int8 shard (127^2 * round_up(d, 64) must stay below 2^31; d <= %lld)",
+                  (long long)d, (long long)I8_MAX_DPAD);
     MDX_CHECK_ARG(layout == MDX_DIM_MAJOR || layout == MDX_ROW_MAJOR, "mdx_index_create: layout %d",
                   layout);
     mdx_index *ix = new mdx_index();
@@ -483,7 +650,8 @@ int mdx_index_create_in(mdx_index **out, const float *src, int64_t n, int64_t d,
     hipStream_t s = (hipStream_t)stream;
     uint32_t *cell = storage == MDX_F32 ? (uint32_t *)((char *)ix->tiles + ix->bytes) : nullptr;
     if (cell && hipMemsetAsync(cell, 0, 4, s) != hipSuccess) cell = nullptr;
-    int rc = retile(src, n, d, layout, nullptr, ix->tiles, ix->RT_pad, ix->KB, s, storage, cell);
+    if (storage == MDX_I8) ix->scales = (float *)((char *)ix->tiles + ix->RT_pad * ix->KB * 1024);
+    int rc = retile(src, n, d, layout, nullptr, ix->tiles, ix->RT_pad, ix->KB, s, storage, cell, ix->scales);
     if (rc == MDX_OK && cell) {
         // index creation is the call of this path that may synchronise: the maximum comes back with the build
         if (hipMemcpyAsync(&ix->max_bits, cell, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
@@ -530,7 +698,33 @@ int mdx_index_info(const mdx_index *ix, int64_t *n, int64_t *d, int64_t *row_off
 int64_t mdx_scores_workspace(int64_t nq, int64_t d)
 {
     if (nq <= 0 || d <= 0) return 0;
-    return round_up(nq, TILE_ROWS) * round_up(d, 64) * 4;   // fp32 tiles; an fp16 shard uses half of it
+    return round_up(nq, TILE_ROWS) * round_up(d, 64) * 4;   // fp32 tiles; an fp16 shard uses half of it, an int8 one a quarter + the scales
+}
+
+static const char *storage_name(int storage) { return storage == MDX_F16 ? "fp16" : storage == MDX_I8 ? "int8" : "fp32"; }
+
+int mdx_quantize_i8(const float *src, int64_t n, int64_t d, int layout, int8_t *codes, float *scales, void *stream)
+{
+    MDX_CHECK_ARG(src && codes && scales, "mdx_quantize_i8: NULL pointer");
+    MDX_CHECK_ARG(n > 0 && d > 0, "mdx_quantize_i8: n=%lld d=%lld must be positive", (long long)n, (long long)d);
+    MDX_CHECK_ARG(round_up(d, 64) <= I8_MAX_DPAD, "mdx_quantize_i8: d=%lld too large (127^2 * round_up(d, 64) must stay below 2^31; d <= %lld)",
+                  (long long)d, (long long)I8_MAX_DPAD);
+    MDX_CHECK_ARG(layout == MDX_DIM_MAJOR || layout == MDX_ROW_MAJOR, "mdx_quantize_i8: layout %d", layout);
+    MDX_CHECK_ARG(ceil_div(n, (int64_t)4) < (1ll << 31), "mdx_quantize_i8: n=%lld too large for one launch", (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    const bool rowmajor = layout == MDX_ROW_MAJOR;
+    const int64_t blocks = ceil_div(n * d, (int64_t)256);
+    const dim3 block(256), grid_q((unsigned)(blocks < 65536 ? blocks : 65536)), grid_rows((unsigned)ceil_div(n, (int64_t)256));
+    if (rowmajor) {
+        hipLaunchKernelGGL(i8_absmax_kernel<true>, dim3((unsigned)ceil_div(n, (int64_t)4)), block, 0, s, src, n, d, (const float *)nullptr, scales, n);
+        hipLaunchKernelGGL(quantize_i8_kernel<true>, grid_q, block, 0, s, src, n, d, (const float *)scales, codes);
+    } else {
+        hipLaunchKernelGGL(i8_absmax_kernel<false>, grid_rows, block, 0, s, src, n, d, (const float *)nullptr, scales, n);
+        hipLaunchKernelGGL(quantize_i8_kernel<false>, grid_q, block, 0, s, src, n, d, (const float *)scales, codes);
+    }
+    hipLaunchKernelGGL(i8_scale_kernel, grid_rows, block, 0, s, scales, n);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
 }
 
 static int scores_impl(const mdx_index *ix, const float *queries, int64_t nq, int qlayout, const float *center, float *scores,
@@ -548,7 +742,7 @@ int mdx_scores_p2p(const mdx_index *ix, const float *queries, int64_t nq, int ql
                    void *workspace, int64_t workspace_bytes, void *stream)
 {
     MDX_CHECK_ARG(ix && queries && p2p, "mdx_scores_p2p: NULL pointer");
-    MDX_CHECK_ARG(ix->storage == MDX_F32, "mdx_scores_p2p: an fp32 shard is needed (this one is stored as fp16)");
+    MDX_CHECK_ARG(ix->storage == MDX_F32, "mdx_scores_p2p: an fp32 shard is needed (this one is stored as %s)", storage_name(ix->storage));
     MDX_CHECK_ARG(nq > 0 && nq <= MAX_QT * TILE_ROWS, "mdx_scores_p2p: nq=%lld, 1..%d supported", (long long)nq, MAX_QT * TILE_ROWS);
     float *const *rows = nullptr;
     if (!p2p_route(p2p, nq, &rows)) {
@@ -573,6 +767,31 @@ static int scores_impl(const mdx_index *ix, const float *queries, int64_t nq, in
     hipStream_t s = (hipStream_t)stream;
     f32x4 *qtiles = (f32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS);
+    if (ix->storage == MDX_I8) {
+        // int8 query tiles (QT_total * KB KiB), then one scale per padded query: round_up(nq, 16) * (d_pad + 4) bytes <= need
+        float *q_scale = (float *)((char *)workspace + QT_total * ix->KB * 1024);
+        int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, s, MDX_I8, nullptr, q_scale);
+        if (rc != MDX_OK) return rc;
+        const bool r2 = ix->RT >= 2048;           // >= 32 768 rows: 128-row workgroups
+        const int64_t full_passes = QT_total / MAX_QT;
+        for (int64_t p0 = 0; p0 < full_passes; p0 += 32768) {        // grid.y < 65 536
+            const int passes = (int)((full_passes - p0) < 32768 ? (full_passes - p0) : 32768);
+            const int64_t q0 = p0 * MAX_QT * TILE_ROWS;
+            rc = dispatch_i8(MAX_QT, r2, ix->tiles, ix->scales, qtiles + p0 * MAX_QT * ix->KB * 64, q_scale + q0, scores + q0 * ix->n, ix->n,
+                             ix->RT, (int)ix->KB, (int)((int64_t)passes * MAX_QT * TILE_ROWS), s, passes);
+            if (rc != MDX_OK) return rc;
+            MDX_LAUNCH_CHECK();
+        }
+        const int64_t qt0 = full_passes * MAX_QT;
+        if (qt0 < QT_total) {
+            const int64_t q0 = qt0 * TILE_ROWS;
+            rc = dispatch_i8((int)(QT_total - qt0), r2, ix->tiles, ix->scales, qtiles + qt0 * ix->KB * 64, q_scale + q0, scores + q0 * ix->n,
+                             ix->n, ix->RT, (int)ix->KB, (int)(nq - q0), s, 1);
+            if (rc != MDX_OK) return rc;
+            MDX_LAUNCH_CHECK();
+        }
+        return MDX_OK;
+    }
     int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, s, ix->storage);
     if (rc != MDX_OK) return rc;
 
@@ -671,7 +890,8 @@ int mdx_scores_ex(const mdx_index *ix, const float *queries, int64_t nq, int qla
     if (compute == MDX_F32_CHAIN) return mdx_scores(ix, queries, nq, qlayout, center, scores, workspace, workspace_bytes, stream);
     MDX_CHECK_ARG(compute == MDX_F32_SPLIT3 || compute == MDX_F32_SPLIT2, "mdx_scores_ex: compute mode %d", compute);
     MDX_CHECK_ARG(ix && queries && scores, "mdx_scores_ex: NULL pointer");
-    MDX_CHECK_ARG(ix->storage == MDX_F32, "mdx_scores_ex: the split-precision modes multiply an fp32 shard (this one is stored as fp16)");
+    MDX_CHECK_ARG(ix->storage == MDX_F32, "mdx_scores_ex: the split-precision modes multiply an fp32 shard (this one is stored as %s)",
+                  storage_name(ix->storage));
     MDX_CHECK_ARG(nq > 0 && nq < (1 << 20), "mdx_scores_ex: nq=%lld", (long long)nq);
     MDX_CHECK_ARG(qlayout == MDX_DIM_MAJOR || qlayout == MDX_ROW_MAJOR, "mdx_scores_ex: qlayout %d", qlayout);
     const int64_t need = mdx_scores_workspace_ex(nq, ix->d, compute);

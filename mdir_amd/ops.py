@@ -398,6 +398,21 @@ def conv1x1_bn_act(x, weight_t, running_mean, running_var, weight=None, bias=Non
 
 # ----------------------------------------------------------------------- index
 
+def quantize_i8(vecs, layout="ND"):
+    """``(codes int8 [N, D], scales fp32 [N])``: the int8 quantisation of an ``MDX_I8`` shard (``mdx_quantize_i8``; the
+    values ``DescriptorIndex(vecs, layout, storage="i8")`` holds for the same rows, bit for bit).  ``vecs`` is a device tensor,
+    ``[N, D]`` (layout "ND") or ``[D, N]`` (layout "DN")."""
+    vp = _dev(vecs, torch.float32, "vecs")
+    n, d, lay = _layout(vecs, layout, "vecs")
+    if n == 0 or d == 0:
+        raise ValueError("vecs must be non-empty, got %d x %d" % (n, d))
+    codes = torch.empty((n, d), dtype=torch.int8, device=vecs.device)
+    scales = torch.empty(n, dtype=torch.float32, device=vecs.device)
+    with torch.cuda.device(vecs.device):
+        check(_lib.lib().mdx_quantize_i8(vp, n, d, lay, _vp(codes.data_ptr()), _vp(scales.data_ptr()), _stream()), "mdx_quantize_i8")
+    return codes, scales
+
+
 class DescriptorIndex:
     """A resident, re-tiled shard of descriptors (``mdx_index``).
 
@@ -406,7 +421,14 @@ class DescriptorIndex:
 
     def __init__(self, vecs, layout="DN", row_offset=0, storage="f32"):
         """``storage="f16"`` keeps the shard (and each call's queries) in fp16 and uses the fp16
-        MFMA with fp32 accumulation: half the HBM bytes, ~1e-3 relative score error."""
+        MFMA with fp32 accumulation: half the HBM bytes, ~1e-3 relative score error.
+
+        ``storage="i8"`` keeps every row as int8 codes and one fp32 scale (a quarter of the fp32 bytes) and multiplies on
+        the int8 MFMA with exact int32 accumulation.  The scores are defined to the bit (``include/mdx.h`` ``MDX_I8``): a row
+        ``x`` (a query: ``q - center``) has ``a = max|x|``, codes ``clamp(rint(x * (127/a)), -127, 127)`` and scale ``a/127``
+        (all fp32, round to nearest even; ``a == 0``: zero codes and scale), and
+        ``score = float(sum_k c_q,k c_i,k) * (scale_i * scale_q)``; :func:`quantize_i8` returns the codes and scales.
+        ``d`` <= 133 120; split-precision ``compute`` modes and the direct-store exchange need an fp32 shard."""
         self._h = None
         self.storage = storage
         vp = _dev(vecs, torch.float32, "vecs")

@@ -13,7 +13,8 @@ The default ``ranking="positions"`` feeds compute_map from ``mdx_rank_of`` (iden
 asserted in the tests and in bench.py -- without an N-long sort; the score object exposes
 nothing but the APs); ``ranking="full"`` runs the reference's dot + argsort + compute_map
 sequence literally.  ``storage="f16"`` (criterion key, not in the reference) keeps the database shard in
-fp16 for the fp16 MFMA -- BASELINE.json configs[4].  ``similarity="split3"`` (criterion key, not in the reference) takes
+fp16 for the fp16 MFMA -- BASELINE.json configs[4]; ``storage="i8"`` keeps it as int8 codes with one fp32 scale per row
+on the int8 MFMA (a quarter of the fp32 bytes; scores defined to the bit by include/mdx.h ``MDX_I8``).  ``similarity="split3"`` (criterion key, not in the reference) takes
 the LABELLED split-precision form of the dot product on the same fp32 shard (three bf16 pieces per operand on the bf16
 MFMA: 0.75 of the exact kernel's time, scores within 2e-6 of it; ``"split2"``: two fp16 pieces with a scaled residual,
 block floating point, 0.63 of the exact kernel's time, same bound for data of ordinary dynamic range; default ``"exact"`` =
@@ -93,8 +94,10 @@ class CirDatasetAp:
         # how the database shard is kept on the GPU: "f32" (the reference's arithmetic: exact k-ordered fp32 chain) or
         # "f16" (BASELINE.json configs[4]: fp16 descriptors on the fp16 MFMA, fp32 accumulation; half the HBM bytes,
         # scores within ~1e-3 relative: a looser, separately tested contract)
+        # "i8" (int8 codes + one fp32 scale per row on the int8 MFMA: a quarter of the fp32 bytes, scores defined to the bit
+        # by include/mdx.h MDX_I8)
         self.storage = params.pop("storage", "f32")
-        assert self.storage in {"f32", "f16"}, self.storage
+        assert self.storage in {"f32", "f16", "i8"}, self.storage
         # how an fp32 shard is multiplied: "exact" (default: the k-ordered fp32 fma chain, the parity contract) or "split3"
         # (labelled second mode, include/mdx.h MDX_F32_SPLIT3)
         self.similarity = params.pop("similarity", "exact")

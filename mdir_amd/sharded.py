@@ -194,7 +194,8 @@ def chunk_bounds(lo, hi, chunks):
 
 class ShardedIndex:
     def __init__(self, local_vecs, layout, n_total, group=None, backend=None, storage="f32", compute="chain"):
-        """``storage``: "f32" (exact chain) or "f16" (fp16 shard on the fp16 MFMA, BASELINE.json configs[4]).
+        """``storage``: "f32" (exact chain), "f16" (fp16 shard on the fp16 MFMA, BASELINE.json configs[4]) or "i8" (int8 codes
+        and one scale per row on the int8 MFMA, include/mdx.h ``MDX_I8``).
         ``compute``: "chain" (default), "split3" or "split2" -- the labelled split-precision similarities on an fp32 shard
         (``DescriptorIndex.scores(compute=...)``, ``include/mdx.h`` ``MDX_F32_SPLIT3``)."""
         self.group = group
@@ -202,7 +203,7 @@ class ShardedIndex:
         if compute not in ("chain", "exact", "split3", "split2"):
             raise ValueError("compute %r" % (compute,))
         if compute in ("split3", "split2") and storage != "f32":
-            raise ValueError("compute=%r multiplies an fp32 shard" % (compute,))
+            raise ValueError("compute=%r multiplies an fp32 shard; this one is stored as %s" % (compute, storage))
         self._score_kw = {"compute": compute} if compute in ("split3", "split2") else {}
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -252,6 +253,10 @@ class ShardedIndex:
         # built at the first step (it is sized by the number of queries); the process group only carries its 64-byte handles.
         self._p2p_on = (os.environ.get("MDIR_AMD_COMM") == "p2p" and self.device.type == "cuda" and storage == "f32"
                         and not self._score_kw)
+        if os.environ.get("MDIR_AMD_COMM") == "p2p" and storage != "f32":
+            import warnings
+            warnings.warn("MDIR_AMD_COMM=p2p: the direct-store exchange multiplies an fp32 shard; this one is stored as %s, "
+                          "so the scores go through the collective exchange" % storage)
         self._p2p = None
         self._use_a2a = True if self._p2p_on else self._probe_all_to_all()
 
@@ -425,7 +430,7 @@ class ShardedIndex:
         """Switch the exchange of ``rank_queries`` between the direct-store form and the collective one at run time (every rank
         must make the same call between the same steps).  Exact fp32 shards only."""
         if on and (self.storage != "f32" or self._score_kw or self.device.type != "cuda"):
-            raise ValueError("the direct-store exchange needs an exact fp32 shard on the GPU")
+            raise ValueError("the direct-store exchange needs an exact fp32 shard on the GPU (storage %s)" % self.storage)
         self._p2p_on = bool(on)
         self.phases = None
 
