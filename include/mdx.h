@@ -563,6 +563,78 @@ int mdx_diffusion_truncated(const int32_t *cols, const float *w, const int32_t *
                             int64_t ld_out, float *residual, int32_t *steps, void *workspace, int64_t workspace_bytes,
                             void *stream);
 
+/* --------------------------------------------------- exact rescoring of shortlists */
+
+/* Exact scores of per-query shortlists (the second stage of a search whose first stage ranks compressed scores):
+ *   rows      fp32 [n, d] row-major at a stride of ld >= d floats (device), read in place
+ *   x_q       = q - center (one fp32 subtraction; none when center == NULL); queries in either mdx_layout, [d, nq] or [nq, d]
+ *   ids       int64 [nq, K] (unique within a query), 1 <= K <= MDX_RESCORE_MAX_K
+ *   score     = the k-ascending fmaf chain from +0.0f of oracle/chain.c: acc = fmaf(x_q,k, rows[id, k], acc), k = 0 .. d-1,
+ *               continued over zeros to round_up(d, 64) as the fp32 kernels of an index do (exact: it can only turn a -0 into
+ *               +0) -- every score is bit-identical to mdx_scores on an fp32 index of the same rows at [q, id], and to
+ *               mdx_scores_rowmajor wherever d % 4 == 0
+ *   out_ids   int64 [nq, K], out_scores fp32 [nq, K]: each query's pairs sorted by mdx_rank_full's order (larger score first,
+ *               -0 == +0, NaN last, equal scores by ascending id; the same key function as the rank kernels)
+ * An id outside [0, n) is never dereferenced: its score is NaN, so it sorts last.  Each query's output bits depend on nothing
+ * but its own inputs (not on nq, not on the other queries).  out_ids may equal ids.  Two launches: the gather and chains (a
+ * workgroup per query and 64 candidates, the rows staged in LDS a KiB at a time) and a per-query bitonic sort in LDS.
+ * MDX_ERR_INVALID, nothing launched, for a NULL pointer, n, d, nq or K < 1, K > MDX_RESCORE_MAX_K, ld < d or an unknown
+ * layout; MDX_ERR_WORKSPACE for fewer than mdx_rescore_workspace(nq, K, d) bytes. */
+#define MDX_RESCORE_MAX_K 4096
+/* round_up(4 nq K, 256) bytes (the unsorted scores); 0 for nq, K or d < 1 or K > MDX_RESCORE_MAX_K. */
+int64_t mdx_rescore_workspace(int64_t nq, int64_t K, int64_t d);
+int mdx_rescore(const float *rows, int64_t n, int64_t d, int64_t ld, const float *queries, int64_t nq, int qlayout,
+                const float *center, const int64_t *ids, int64_t K, int64_t *out_ids, float *out_scores, void *workspace,
+                int64_t workspace_bytes, void *stream);
+
+/* What the certificate needs to know of an MDX_I8 shard, written on the device by mdx_index_i8_bounds:
+ *   s_max = max_i scale_i        s_min = the smallest nonzero scale_i (+inf when there is none)
+ *   l_max = max_i scale_i ||c_i||_1 (exact in float64: a 24-bit scale times an integer below 2^25)
+ *   flag  = 1 when some row is outside the int8 contract as the shard can tell: a non-finite scale (an infinite element) or
+ *           0 < scale < 2^-106 (every row with 0 < a < 2^-100, and a few just above it), else 0.
+ * A NaN element that is not a row's absmax leaves no trace in the codes; it needs none: the row's chain score is NaN, which
+ * ranks after every number in the exact order, so it cannot enter an exact top-c ahead of a certified entry.  Rows of scale 0
+ * (all zero) score exactly 0 on both paths.  Only the maxima and minima are reduced (order-free), so the values are the same
+ * on every run. */
+typedef struct mdx_i8_bounds {
+    double s_max, s_min, l_max;
+    int32_t flag, reserved;
+} mdx_i8_bounds;
+/* A reduction over the codes and scales of an MDX_I8 index into `bounds` (device, one mdx_i8_bounds): enqueued only, two
+ * launches, nothing of the index is changed (a host runs it once per index and keeps the result).  MDX_ERR_INVALID for a
+ * NULL pointer or an index that is not MDX_I8. */
+int mdx_index_i8_bounds(const mdx_index *index, mdx_i8_bounds *bounds, void *stream);
+
+/* The certificate of a rescored int8 shortlist: a depth c_q such that the first c_q entries of mdx_rescore's output are,
+ * bit for bit (ids and scores), the first c_q entries of the exact ranking -- mdx_topk on mdx_scores of an fp32 index of the
+ * same rows.
+ *   scores  fp32 [nq, K]: mdx_rescore's sorted out_scores for the shortlist ids = mdx_topk(int8 scores, K) of the index
+ *   t       fp32 [nq]: t_q = the K-th int8 shortlist score (top_scores[:, K-1] of that mdx_topk)
+ *   queries / d / qlayout / center: those of the int8 scores (x_q = q - center); bounds: mdx_index_i8_bounds of that index
+ *   n       the rows of the index; K <= n
+ *   upper   fp32 [nq] = U_q below, rounded up;  depth int32 [nq] = c_q
+ * Proof.  Every row i outside the shortlist ranks after it in the int8 order, so s_i <= t_q (NaN t_q: no certificate).  By the
+ * MDX_I8 bound (mdx_storage), with E = 1/2 + 2^-15 and scale_q the query's int8 scale,
+ *     x_i.x_q <= s_i + 2^-22 |s_i| + scale_i E ||x_q||_1 + scale_i ||c_i||_1 scale_q E
+ *             <= t_q + 2^-22 |t_q| + S_max E ||x_q||_1 + L_max scale_q E                 (s + 2^-22|s| increases with s)
+ * The chain is a recursive fma sum: |chain_i - x_i.x_q| <= gamma_d sum_k |x_i,k x_q,k| + d 2^-149, gamma_d = d u / (1 - d u),
+ * u = 2^-24 (one rounding per fma; the d 2^-149 covers the absolute error of results in the subnormal range), and
+ * sum_k |x_i,k x_q,k| <= a_i ||x_q||_1 <= 127 S_max (1 + 2^-22) ||x_q||_1 =: B_q (a_i <= 127 scale_i / (1 - u)).  Hence
+ *     chain_i <= U_q = t_q + 2^-22 |t_q| + S_max E ||x_q||_1 + L_max scale_q E + gamma_d B_q + d 2^-149
+ * for every row outside the shortlist whose chain score is a number.  The shortlist's entries are exact and sorted by the
+ * ranking's order, so its first c_q entries, all with a score > U_q (strictly), precede every other row of the database:
+ *     c_q = the number of leading entries with score > U_q;  c_q = K when K == n (no row is outside; upper = -inf).
+ * Rounding.  U_q is evaluated in float64 from the fp32 inputs (||x_q||_1 as a float64 sum of the fp32 |x_q,k|), inflated by
+ * (d + 16) 2^-52 times the sum of the magnitudes of its terms -- more than all float64 rounding of the evaluation -- and then
+ * rounded to fp32 upwards (round to nearest; one step up if that went down).  So rounding can only raise U_q.
+ * No certificate (c_q = 0) when K < n and: bounds->flag is set; x_q holds a non-finite value or 0 < max|x_q| < 2^-100 (outside
+ * the int8 contract); t_q is NaN; S_min scale_q < 2^-126 (the scale product could underflow, which the MDX_I8 bound excludes);
+ * B_q >= 2^126 (a partial sum could overflow); d u >= 1/2; or U_q is not finite.
+ * One workgroup per query, fixed-order reductions: bit-identical run to run and independent of nq.  MDX_ERR_INVALID, nothing
+ * launched, for a NULL pointer, nq, K, d or n < 1, K > min(n, MDX_RESCORE_MAX_K) or an unknown layout. */
+int mdx_rescore_certify(const float *scores, int64_t nq, int64_t K, const float *t, const float *queries, int64_t d, int qlayout,
+                        const float *center, const mdx_i8_bounds *bounds, int64_t n, float *upper, int32_t *depth, void *stream);
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

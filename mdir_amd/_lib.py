@@ -82,6 +82,10 @@ def _declare(lib):
         "mdx_index_bytes": (i64, [i64, i64, i32]),
         "mdx_index_create_in": (i32, [pp, p, i64, i64, i32, i64, i32, p, i64, p]),
         "mdx_index_destroy": (i32, [p]),
+        "mdx_rescore_workspace": (i64, [i64, i64, i64]),
+        "mdx_rescore": (i32, [p, i64, i64, i64, p, i64, i32, p, p, i64, p, p, p, i64, p]),
+        "mdx_index_i8_bounds": (i32, [p, p, p]),
+        "mdx_rescore_certify": (i32, [p, i64, i64, p, p, i64, i32, p, p, i64, p, p, p]),
         "mdx_index_info": (i32, [p, pi64, pi64, pi64, pi64]),
         "mdx_scores_workspace": (i64, [i64, i64]),
         "mdx_quantize_i8": (i32, [p, i64, i64, i32, p, p, p]),
@@ -142,7 +146,8 @@ EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac
            "mdx_scores", "mdx_scores_rowmajor", "mdx_scores_workspace_ex", "mdx_scores_ex", "mdx_rank_workspace", "mdx_rank_full", "mdx_rank_full_segments", "mdx_topk", "mdx_rank_of", "mdx_rank_positions",
            "mdx_gather_scores", "mdx_rank_count", "mdx_knn_aggregate", "mdx_knn_graph_workspace", "mdx_knn_graph",
            "mdx_diffusion_workspace", "mdx_diffusion", "mdx_knn_graph_weights", "mdx_diffusion_truncated_workspace",
-           "mdx_diffusion_truncated", "mdx_conv1x1_transpose_weights", "mdx_conv1x1_bn_act", "mdx_clahe_workspace", "mdx_clahe_u8_to_chw", "mdx_gram_f64_workspace", "mdx_gram_f64", "mdx_project_f64_workspace", "mdx_project_f64", "mdx_l2n_cols_f64", "mdx_comm_unique_id", "mdx_comm_init",
+           "mdx_diffusion_truncated", "mdx_rescore_workspace", "mdx_rescore", "mdx_index_i8_bounds", "mdx_rescore_certify",
+           "mdx_conv1x1_transpose_weights", "mdx_conv1x1_bn_act", "mdx_clahe_workspace", "mdx_clahe_u8_to_chw", "mdx_gram_f64_workspace", "mdx_gram_f64", "mdx_project_f64_workspace", "mdx_project_f64", "mdx_l2n_cols_f64", "mdx_comm_unique_id", "mdx_comm_init",
            "mdx_comm_destroy", "mdx_comm_info", "mdx_query_bounds", "mdx_allgather_scores", "mdx_exchange_scores",
            "mdx_p2p_create", "mdx_p2p_connect", "mdx_p2p_connect_ptrs", "mdx_p2p_base", "mdx_p2p_bytes", "mdx_scores_p2p", "mdx_p2p_close_step",
            "mdx_p2p_status", "mdx_p2p_destroy")

@@ -14,6 +14,9 @@ void set_error(const char *fmt, ...);
 // mdx_p2p.hip: the row pointers of the open step of a connected direct-store exchange (false: not connected / another nq)
 bool p2p_route(const mdx_p2p *p, int64_t nq, float *const **rows);
 
+// mdx_index.hip: the codes (tiles of 16 rows x 64 k), scales and geometry of an MDX_I8 shard (false: another storage)
+bool i8_view(const mdx_index *ix, const void **tiles, const float **scales, int64_t *n, int64_t *rt, int64_t *kb);
+
 // mdx_rank.hip: decides once per device how the sort ranks inside a wave (may synchronise `s`); 0 = not decided (capturing)
 int probe_lds_order(hipStream_t s);
 

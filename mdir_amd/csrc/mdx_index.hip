@@ -518,6 +518,17 @@ struct mdx_index {
     uint32_t max_bits;  // fp32 shards: bit pattern of the largest finite |x| (read back once at creation): the scale of MDX_F32_SPLIT2
 };
 
+bool mdx::i8_view(const mdx_index *ix, const void **tiles, const float **scales, int64_t *n, int64_t *rt, int64_t *kb)
+{
+    if (!ix || ix->storage != MDX_I8) return false;
+    *tiles = ix->tiles;
+    *scales = ix->scales;
+    *n = ix->n;
+    *rt = ix->RT;
+    *kb = ix->KB;
+    return true;
+}
+
 extern "C" {
 
 int mdx_abi_version(void) { return MDX_ABI_VERSION; }

@@ -366,3 +366,29 @@ def compute_map_and_print_from_scores(dataset, scores, gnd, kappas=[1, 5, 10]):
     """Same as :func:`compute_map_and_print`, from device scores ``[Q,N]`` (one counting pass for all protocol levels)."""
     positions = _score_positions(scores, gnd)
     return _evaluate(dataset, gnd, kappas, lambda g, k: compute_map_from_scores(scores, g, k, _positions=positions), positions)
+
+
+def positions_composite(scores, head, id_lists):
+    """Positions of ids in the composite ranking whose first K entries are ``head`` (int64 ``[Q, K]`` on the device) and whose
+    rest is the order of ``scores`` ``[Q, N]``, where ``head[q]`` holds exactly the ids of the first K of ``rank_full(scores)``
+    (a rescored shortlist): an id at a score position below K takes its position in ``head``, every other id keeps its own."""
+    from . import ops
+    K = head.shape[1]
+    by_scores = positions_from_scores(scores, id_lists)
+    pos, off = ops.rank_positions(head, id_lists)
+    pos = pos.cpu().numpy()
+    out = []
+    for q, p in enumerate(by_scores):
+        h = pos[off[q]:off[q + 1]]
+        inside = p < K
+        if np.any(h[inside] < 0):
+            raise ValueError("head of query %d is not the first %d rows of the ranking of its scores" % (q, K))
+        out.append(np.where(inside, h, p))
+    return out
+
+
+def compute_map_and_print_composite(dataset, scores, head, gnd, kappas=[1, 5, 10]):
+    """:func:`compute_map_and_print` of the composite ranking of :func:`positions_composite` (same APs as the ranking
+    ``rank_full(scores)`` with its first K columns replaced by ``head``)."""
+    positions = _positions_of_rows(scores.shape[1], gnd, lambda lists: positions_composite(scores, head, lists))
+    return _evaluate(dataset, gnd, kappas, lambda g, k: positions.map(g, k), positions)

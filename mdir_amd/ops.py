@@ -505,7 +505,23 @@ class DescriptorIndex:
         with torch.cuda.device(self.device):
             check(_lib.lib().mdx_scores_p2p(self._h, qp, nq, lay, cp, p2p._h, _vp(ws.data_ptr()), need, _stream()), "mdx_scores_p2p")
 
+    def i8_bounds(self):
+        """Device tensor (float64 ``[4]``, the bytes of ``mdx_i8_bounds``) of this int8 shard: ``S_max``, ``S_min`` (smallest
+        nonzero scale), ``L_max = max scale_i ||c_i||_1`` and the out-of-contract flag (:func:`unpack_i8_bounds` reads it on the
+        host).  Reduced once per index (``mdx_index_i8_bounds``) and kept; what :func:`rescore_certify` needs."""
+        if self._h is None:
+            raise RuntimeError("index is closed")
+        if self.storage != "i8":
+            raise ValueError("i8_bounds needs an int8 shard; this one is stored as %s" % self.storage)
+        if getattr(self, "_i8_bounds", None) is None:
+            b = torch.empty(4, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                check(_lib.lib().mdx_index_i8_bounds(self._h, _vp(b.data_ptr()), _stream()), "mdx_index_i8_bounds")
+            self._i8_bounds = b
+        return self._i8_bounds
+
     def close(self):
+        self._i8_bounds = None
         if getattr(self, "_h", None) is not None and self._h.value:
             h, self._h = self._h, None
             check(_lib.lib().mdx_index_destroy(h), "mdx_index_destroy")
@@ -610,6 +626,83 @@ def topk(scores, k, id_offset=0, workspace=None):
         check(_lib.lib().mdx_topk(sp, n, nq, int(k), int(id_offset), _vp(ids.data_ptr()), _vp(vals.data_ptr()),
                                   _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_topk")
     return ids, vals
+
+
+RESCORE_MAX_K = 4096              # include/mdx.h MDX_RESCORE_MAX_K: one query's shortlist is sorted in LDS
+
+
+def rescore(rows, queries, ids, qlayout="ND", center=None):
+    """``(ids int64 [nq, K], scores fp32 [nq, K])``: the exact fp32 chain scores of each query's shortlist ``ids`` (int64
+    ``[nq, K]``, unique within a query, ``K <= 4096``) against ``rows`` (fp32 ``[n, d]`` on the device, rows contiguous at any
+    stride), sorted by :func:`rank_full`'s order (``mdx_rescore``).  Every score is bit-identical to
+    ``DescriptorIndex(rows, "ND").scores(queries, qlayout, center)`` at the same id; an id outside ``[0, n)`` scores NaN and
+    sorts last."""
+    rp, ld = _rows(rows, "rows")
+    n, d = rows.shape
+    nq, dq, lay = _layout(queries, qlayout, "queries")
+    if dq != d:
+        raise ValueError("query dimension %d != rows dimension %d" % (dq, d))
+    qp = _dev(queries, torch.float32, "queries")
+    cp = _dev(center, torch.float32, "center") if center is not None else None
+    if center is not None and center.numel() != d:
+        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    _dev(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[0] != nq:
+        raise ValueError("ids must be [%d, K], got %s" % (nq, tuple(ids.shape)))
+    K = ids.shape[1]
+    if n < 1 or d < 1 or nq < 1 or not 1 <= K <= RESCORE_MAX_K:
+        raise ValueError("rescore: n=%d d=%d nq=%d must be >= 1 and K=%d in [1, %d]" % (n, d, nq, K, RESCORE_MAX_K))
+    out_ids = torch.empty((nq, K), dtype=torch.int64, device=rows.device)
+    out_scores = torch.empty((nq, K), dtype=torch.float32, device=rows.device)
+    h = _lib.lib()
+    need = h.mdx_rescore_workspace(nq, K, d)
+    ws = _workspace(need, rows.device)
+    with _on(rows):
+        check(h.mdx_rescore(rp, n, d, ld, qp, nq, lay, cp, _vp(ids.data_ptr()), K, _vp(out_ids.data_ptr()),
+                            _vp(out_scores.data_ptr()), _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_rescore")
+    return out_ids, out_scores
+
+
+def unpack_i8_bounds(bounds):
+    """The values of :meth:`DescriptorIndex.i8_bounds` on the host: ``{"s_max", "s_min", "l_max": float, "flag": int}``."""
+    raw = bounds.cpu().numpy()
+    return {"s_max": float(raw[0]), "s_min": float(raw[1]), "l_max": float(raw[2]),
+            "flag": int(raw[3:4].view(np.int32)[0])}
+
+
+def rescore_certify(scores, t, queries, bounds, n, qlayout="ND", center=None):
+    """``(depth int32 [nq], upper fp32 [nq])`` (``mdx_rescore_certify``, the proof in ``include/mdx.h``): the first ``depth[q]``
+    entries of :func:`rescore`'s sorted output for the shortlist ``topk(int8 scores, K)`` are, bit for bit, the first entries
+    of the exact fp32 ranking.  ``scores`` fp32 ``[nq, K]`` (rescore's sorted scores), ``t`` fp32 ``[nq]`` (the K-th int8
+    shortlist score, ``top_scores[:, K-1]``), ``queries`` / ``center`` those of the int8 scores, ``bounds`` of
+    :meth:`DescriptorIndex.i8_bounds`, ``n`` the index's rows.  ``upper`` is the bound U_q every row outside the shortlist
+    stays under."""
+    _dev(scores, torch.float32, "scores")
+    if scores.dim() != 2:
+        raise ValueError("scores must be [nq, K]")
+    nq, K = scores.shape
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.shape[0] != nq:
+        raise ValueError("t must be a [%d] tensor" % nq)
+    t = t.contiguous()
+    tp = _dev(t, torch.float32, "t")
+    nqq, d, lay = _layout(queries, qlayout, "queries")
+    if nqq != nq:
+        raise ValueError("queries hold %d queries, scores %d" % (nqq, nq))
+    qp = _dev(queries, torch.float32, "queries")
+    cp = _dev(center, torch.float32, "center") if center is not None else None
+    if center is not None and center.numel() != d:
+        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    bp = _dev(bounds, torch.float64, "bounds")
+    if bounds.numel() != 4:
+        raise ValueError("bounds: the float64 [4] tensor of DescriptorIndex.i8_bounds()")
+    if not 1 <= K <= min(int(n), RESCORE_MAX_K):
+        raise ValueError("K=%d must be in [1, min(n=%d, %d)]" % (K, n, RESCORE_MAX_K))
+    upper = torch.empty(nq, dtype=torch.float32, device=scores.device)
+    depth = torch.empty(nq, dtype=torch.int32, device=scores.device)
+    with _on(scores):
+        check(_lib.lib().mdx_rescore_certify(_vp(scores.data_ptr()), nq, K, tp, qp, d, lay, cp, bp, int(n), _vp(upper.data_ptr()),
+                                             _vp(depth.data_ptr()), _stream()), "mdx_rescore_certify")
+    return depth, upper
 
 
 def _rows(t, what):

@@ -25,6 +25,10 @@ database.  Single-process only for now.  ``diffusion: {k, kq, gamma, alpha, iter
 sub-key optional, defaults of the paper's release) re-ranks by diffusion on a mutual kNN graph of the database
 (``rerank.diffusion``), after DBA when both are set; not together with query_expansion; single-process only.  The optional
 sub-key ``truncate: R`` (``kq <= R <= 4096``; no default) solves each query on the subgraph of its top-R rows instead.
+``rescore: {shortlist: K}`` (criterion key, ``1 <= K <= 4096``, clamped to N; needs ``storage: i8`` or ``f16``;
+single-process; not with the re-ranking keys) rescores each query's top-K rows of the compressed scores exactly
+(``ops.rescore``, the fp32 chain) and ranks by the composite: the rescored top-K, then every other row in the compressed
+order.  For int8 it prints the certified depth (``ops.rescore_certify``) per query: min / median / max.
 """
 import gzip
 import json
@@ -33,9 +37,11 @@ import math
 import os.path
 from collections import OrderedDict
 
+import numpy as np
+
 from . import ops, rerank
 from .datasets import configdataset, get_data_root, initialize_transforms
-from .evaluate import compute_map_and_print, compute_map_and_print_from_scores
+from .evaluate import compute_map_and_print, compute_map_and_print_composite, compute_map_and_print_from_scores
 from .networks import extract_vectors_device
 from .scenario import StopWatch, path_join
 from .trace import range_
@@ -110,6 +116,15 @@ class CirDatasetAp:
         self.diffusion = _diffusion_params(params.pop("diffusion", None))
         if self.diffusion and self.query_expansion:
             raise ValueError("diffusion together with query_expansion is not supported: choose one")
+        # exact rescoring of a shortlist of the compressed scores (not in the reference): {shortlist: K}; None = off
+        self.rescore = _rescore_params(params.pop("rescore", None))
+        if self.rescore:
+            if self.storage not in {"i8", "f16"}:
+                raise ValueError("rescore: rescores the shortlist of an int8 or fp16 shard (storage: i8 / f16); storage is %s, "
+                                 "whose scores are already exact" % self.storage)
+            others = [k for k in ("query_expansion", "database_augmentation", "diffusion") if getattr(self, k)]
+            if others:
+                raise ValueError("rescore together with %s is not supported" % " / ".join(others))
         if isinstance(self.dataset, dict):
             assert self.dataset.keys() == {"name", "queries", "db", "imgdir"}
             imgdir = self.dataset["imgdir"]
@@ -138,6 +153,8 @@ class CirDatasetAp:
         if _world_size() > 1 and self.diffusion:
             raise ValueError("%s: diffusion re-ranks in a single process (the graph spans the whole database); this run has "
                              "%d ranks" % (self.dataset, _world_size()))
+        if _world_size() > 1 and self.rescore:
+            raise ValueError("%s: rescore runs in a single process for now; this run has %d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1:
             # one process per GPU (torchrun eval.py ...): every rank extracts its slice of the
             # database, which stays resident as its shard; same rows go to the logger on every rank
@@ -187,7 +204,9 @@ class CirDatasetAp:
                     scores = rerank.diffusion(qvecs, vecs, graph, kq=p["kq"], alpha=p["alpha"], iters=p["iters"],
                                               tol=p["tol"], scores=scores, truncate=truncate)
                     graph.close()
-            if self.ranking == "full":
+            if self.rescore:
+                averages, scores_per_query = self._rescored_map(vecs, qvecs, scores, index)
+            elif self.ranking == "full":
                 with range_("ranking"):
                     ranks = ops.rank_full(scores)                   # [Q,N] = argsort(-scores, axis=0).T
                 averages, scores_per_query = compute_map_and_print(self.dataset, ranks.t(), self.gnd)
@@ -197,6 +216,27 @@ class CirDatasetAp:
         if index is not None:
             index.close()
         self._log(logger, stopwatch, averages, scores_per_query)
+
+    def _rescored_map(self, vecs, qvecs, scores, index):
+        """mAP of the composite ranking: each query's top-K of the compressed ``scores`` rescored exactly and sorted, then
+        every other row in the compressed order (the shortlist is exactly the first K of ``rank_full(scores)``, so the
+        positions beyond K do not move)."""
+        n = scores.shape[1]
+        K = min(self.rescore["shortlist"], n)
+        with range_("rescore"):
+            top_ids, top_scores = ops.topk(scores, K)
+            ids, sc = ops.rescore(vecs, qvecs, top_ids, "ND")
+        if self.storage == "i8":
+            depth, _ = ops.rescore_certify(sc, top_scores[:, K - 1], qvecs, index.i8_bounds(), n, "ND")
+            c = depth.cpu().numpy()
+            print(">> {}: rescored top-{}, certified depth min {} / median {:g} / max {}".format(
+                self.dataset, K, int(c.min()), float(np.median(c)), int(c.max())))
+        if self.ranking == "full":
+            with range_("ranking"):
+                ranks = ops.rank_full(scores)
+                ranks[:, :K] = ids
+            return compute_map_and_print(self.dataset, ranks.t(), self.gnd)
+        return compute_map_and_print_composite(self.dataset, scores, ids, self.gnd)
 
     @staticmethod
     def _log(logger, stopwatch, averages, scores_per_query):
@@ -253,6 +293,18 @@ def _diffusion_params(value):
             raise ValueError("diffusion: truncate must be an integer in [kq, %d] = [%d, %d], got %r"
                              % (ops.DIFFUSION_MAX_R, out["kq"], ops.DIFFUSION_MAX_R, x))
     return out
+
+
+def _rescore_params(value):
+    """``{shortlist: K}`` of the ``rescore`` criterion key, validated (None: the key is absent)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict) or set(value) != {"shortlist"}:
+        raise ValueError("rescore: a mapping with exactly the key shortlist, got %r" % (value,))
+    x = value["shortlist"]
+    if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= ops.RESCORE_MAX_K:
+        raise ValueError("rescore: shortlist must be an integer in [1, %d], got %r" % (ops.RESCORE_MAX_K, x))
+    return {"shortlist": x}
 
 
 def _rank_world():
