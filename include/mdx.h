@@ -635,6 +635,77 @@ int mdx_index_i8_bounds(const mdx_index *index, mdx_i8_bounds *bounds, void *str
 int mdx_rescore_certify(const float *scores, int64_t nq, int64_t K, const float *t, const float *queries, int64_t d, int qlayout,
                         const float *center, const mdx_i8_bounds *bounds, int64_t n, float *upper, int32_t *depth, void *stream);
 
+/* --------------------------------------------- exact range search and self-join */
+
+/* Every pair whose exact score reaches a threshold tau: a range search (queries x database) and a self-join (i < j of one
+ * database), pruned on MDX_I8 shards and decided by the exact chain.
+ *   Exact score of a pair (x in the query role, y in the database role): the fmaf chain of mdx_rescore, acc = fmaf(x_k, y_k, acc)
+ *     from +0, k = 0 .. round_up(d, 64) - 1 over zeros -- bit-identical to mdx_scores on an fp32 index of the database rows.  x =
+ *     q - center for external queries (one fp32 subtraction; mdx_center_rows), the raw row for the self-join.  chain(i, j) ==
+ *     chain(j, i) bitwise: fma is commutative in its two factors, so the self-join computes every unordered pair once.
+ *   Result: every pair with chain >= tau (a NaN score never is); the self-join leaves out i == j and reports i < j only.  CSR over
+ *     the query (over i for the self-join): offsets int64 [m + 1], ids int64 [P], scores fp32 [P]; each segment in mdx_rank_full's
+ *     order (larger score first, -0 == +0, ties by ascending id).  The bits depend on the inputs only -- not on chunking, capacity,
+ *     nq or launch order.
+ *
+ * Pruning bound.  Per row, from its fp32 values x, its codes c and scale of an MDX_I8 shard (mdx_join_stats):
+ *     p = scale,  q >= E ||x||_1,  r >= E scale ||c||_1,  w >= scale + gamma_d max|x| / E,   E = 1/2 + 2^-15
+ *   (fp32, each evaluated in float64, inflated by 1 + (d + 16) 2^-52 -- more than the float64 rounding, ||x||_1 being a sum of d
+ *   terms -- rounded upwards and floored at 2^-149).  For a pair x (query role), y (database role) with int8 score s (mdx_storage):
+ *     |x.y - s| <= scale_y E ||x||_1 + scale_y ||c_y||_1 scale_x E + 2^-22 |s|                      (the MDX_I8 bound)
+ *     |chain - x.y| <= gamma_d sum_k |x_k y_k| + d 2^-149 <= gamma_d max|y| ||x||_1 + d 2^-149       (mdx_rescore_certify)
+ *   so  chain >= tau  =>  s + 2^-22 |s| >= tau - beta_xy  with
+ *     beta_xy = scale_y E ||x||_1 + scale_y ||c_y||_1 scale_x E + gamma_d max|y| ||x||_1 + d 2^-149  <=  q_x w_y + r_y p_x + d 2^-149.
+ *   The bound is symmetric in the roles of the MDX_I8 error terms (and the chain's sum_k |x_k y_k| is), so beta_yx is valid as
+ *   well; the kernel takes the smaller of the two.
+ * Rounding inside the join kernel.  b = fl(fl(fl(q_x w_y) + fl(r_y max(p_x, 2^-149))) + c0) * (1 + 2^-20) rounded, with
+ *   c0 = (d + 2) 2^-149 (exact).  With u = 2^-24, a rounded product of non-negatives is >= its value (1 - u) - 2^-150, a rounded sum
+ *   >= (1 - u) of its value, and (1 - u)^5 (1 + 2^-20) > 1, so b >= q_x w_y + r_y p_x + (d + 2) 2^-149 - 3 2^-150 >= beta + 2^-150.
+ *   A pair is a candidate unless fl(fl(s + fl(2^-21 |s|)) + b) < tau.  fl(2^-21 |s|) >= 2^-21 |s| - 2^-150 and the rounded sum
+ *   s + h loses at most u |s + h| <= (2^-24 + 2^-45) |s|, so fl(s + h) >= s + 2^-22 |s| - 2^-150 and fl(s + h) + b >=
+ *   s + 2^-22 |s| + beta >= tau; rounding is monotone and tau is an fp32 value, so the computed sum is >= tau as well.  The fp32
+ *   evaluation can only enlarge beta: the int8 pass over-selects and never drops a hit.  A NaN score is a candidate.
+ * Pairs the bound does not cover are never pruned (their beta is +inf): rows with a non-finite value (as their scale or their
+ *   ||x||_1 may show nothing); nonzero rows whose scale is below 2^-106 -- every row with 0 < max|x| < 2^-100, among them the rows
+ *   whose max|x| is so small a subnormal that scale = max|x| / 127 rounds to 0: scale c is then 0 and their quantisation error is
+ *   x itself, which no scale-proportional term covers -- or above 2^40 (the score could overflow); and pairs of nonzero scales
+ *   whose fp32 product is below 2^-126 (it may have underflowed).  Only a row with max|x| == 0 (all zero) is covered with scale 0:
+ *   it scores exactly 0 on both paths.  So the result is exact for every input: infinities, NaN rows, zero and subnormal rows.
+ *
+ * Stages (all enqueue only):
+ *   mdx_center_rows      out [n, d] row-major = src - center (center NULL: a copy); the fp32 query rows of a range search
+ *   mdx_join_stats       stats fp32 [n, 4] = {p, q, r, w} of each row of an MDX_I8 index of the fp32 rows `rows` [n, d] at a
+ *                        stride of ld (the rows the index was built from); an fp16 or fp32 index is refused (it has no bound)
+ *   mdx_join_candidates  the join kernel over rows [a_lo, a_hi) of A (a_lo a multiple of MDX_JOIN_BLOCK) against every row of B,
+ *                        both MDX_I8 of one d; symmetric (A == B): j > i only.  pairs[0 .. min(count, capacity)) = i << 32 | j
+ *                        (global rows) of the candidates in no particular order; *count (device int64) = the number of
+ *                        candidates, counted on past the capacity (a caller retries with that size).  No score matrix is written.
+ *   mdx_join_resolve     pairs [P] (each unique) of rows i in [m_lo, m_lo + m): the exact chains of rows_a[i] and rows_b[j] (row-
+ *                        grouped: the pairs are sorted by (i, j) first), the hits, and the CSR of rows m_lo .. m_lo + m - 1 into
+ *                        offsets [m + 1] (offsets[m] = the hits), ids [P], scores [P] (the first offsets[m] entries written).
+ *                        workspace: mdx_join_resolve_workspace(P, m) bytes.
+ *   mdx_range_select     the dense route: the same CSR of an fp32 score matrix [m, n] at a stride of ld (scores_rowmajor or
+ *                        mdx_scores output), hits s >= tau and, for diag >= 0, j > diag + r in row r (the upper triangle of a
+ *                        self-join block whose first row is diag); diag < 0: every column.  offsets [m + 1] are always written;
+ *                        ids / scores only when offsets[m] <= capacity (else the caller retries with offsets[m]).  workspace:
+ *                        mdx_range_select_workspace(m, capacity) bytes.
+ * The final order is a stable radix sort of (row, desc_key(score)) whose input is in (row, id) order; the offsets are a binary
+ * search per row.  MDX_ERR_INVALID, nothing launched, for a NULL pointer, sizes < 1 (n, d, P, m), P, m or a capacity at or above
+ * 2^31, a negative capacity, ld below d (or n), a non-finite tau, a non-int8 index, A and B of different d, symmetric with A != B,
+ * an unknown layout; MDX_ERR_WORKSPACE for a workspace below the size functions' (0 for sizes they refuse). */
+#define MDX_JOIN_BLOCK 128
+int mdx_center_rows(const float *src, int64_t n, int64_t d, int layout, const float *center, float *out, void *stream);
+int mdx_join_stats(const mdx_index *index, const float *rows, int64_t ld, float *stats, void *stream);
+int mdx_join_candidates(const mdx_index *a, const float *stats_a, const mdx_index *b, const float *stats_b, int64_t a_lo, int64_t a_hi,
+                        int symmetric, float tau, uint64_t *pairs, int64_t capacity, int64_t *count, void *stream);
+int64_t mdx_join_resolve_workspace(int64_t P, int64_t m);
+int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs, int64_t P,
+                     float tau, int64_t m_lo, int64_t m, int64_t *offsets, int64_t *ids, float *scores, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+int64_t mdx_range_select_workspace(int64_t m, int64_t capacity);
+int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, float tau, int64_t diag, int64_t *offsets, int64_t *ids,
+                     float *out_scores, int64_t capacity, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -86,6 +86,13 @@ def _declare(lib):
         "mdx_rescore": (i32, [p, i64, i64, i64, p, i64, i32, p, p, i64, p, p, p, i64, p]),
         "mdx_index_i8_bounds": (i32, [p, p, p]),
         "mdx_rescore_certify": (i32, [p, i64, i64, p, p, i64, i32, p, p, i64, p, p, p]),
+        "mdx_center_rows": (i32, [p, i64, i64, i32, p, p, p]),
+        "mdx_join_stats": (i32, [p, p, i64, p, p]),
+        "mdx_join_candidates": (i32, [p, p, p, p, i64, i64, i32, f32, p, i64, p, p]),
+        "mdx_join_resolve_workspace": (i64, [i64, i64]),
+        "mdx_join_resolve": (i32, [p, i64, p, i64, i64, p, i64, f32, i64, i64, p, p, p, p, i64, p]),
+        "mdx_range_select_workspace": (i64, [i64, i64]),
+        "mdx_range_select": (i32, [p, i64, i64, i64, f32, i64, p, p, p, i64, p, i64, p]),
         "mdx_index_info": (i32, [p, pi64, pi64, pi64, pi64]),
         "mdx_scores_workspace": (i64, [i64, i64]),
         "mdx_quantize_i8": (i32, [p, i64, i64, i32, p, p, p]),
@@ -147,6 +154,8 @@ EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac
            "mdx_gather_scores", "mdx_rank_count", "mdx_knn_aggregate", "mdx_knn_graph_workspace", "mdx_knn_graph",
            "mdx_diffusion_workspace", "mdx_diffusion", "mdx_knn_graph_weights", "mdx_diffusion_truncated_workspace",
            "mdx_diffusion_truncated", "mdx_rescore_workspace", "mdx_rescore", "mdx_index_i8_bounds", "mdx_rescore_certify",
+           "mdx_center_rows", "mdx_join_stats", "mdx_join_candidates", "mdx_join_resolve_workspace", "mdx_join_resolve",
+           "mdx_range_select_workspace", "mdx_range_select",
            "mdx_conv1x1_transpose_weights", "mdx_conv1x1_bn_act", "mdx_clahe_workspace", "mdx_clahe_u8_to_chw", "mdx_gram_f64_workspace", "mdx_gram_f64", "mdx_project_f64_workspace", "mdx_project_f64", "mdx_l2n_cols_f64", "mdx_comm_unique_id", "mdx_comm_init",
            "mdx_comm_destroy", "mdx_comm_info", "mdx_query_bounds", "mdx_allgather_scores", "mdx_exchange_scores",
            "mdx_p2p_create", "mdx_p2p_connect", "mdx_p2p_connect_ptrs", "mdx_p2p_base", "mdx_p2p_bytes", "mdx_scores_p2p", "mdx_p2p_close_step",

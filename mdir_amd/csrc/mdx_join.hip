@@ -1,0 +1,670 @@
+// Exact range search and self-join, pruned on the int8 shard (include/mdx.h, "exact range search and self-join").
+//
+//   join_stats_kernel     one wave per row: ||x||_1 (float64), max |x|, finiteness and ||c||_1 of the row's int8 codes ->
+//                         the four per-row factors {scale, q, r, w} of the pruning bound, rounded up to fp32.
+//   join_kernel           one workgroup per (I, J) block of 128 x 128 rows of two int8 shards A and B: both operands are
+//                         staged in LDS a 64-k chunk at a time (double buffer, one barrier per chunk), every wave multiplies
+//                         64 x 64 rows on v_mfma_i32_16x16x64_i8 (exact int32 sums), and the epilogue forms the MDX_I8 score
+//                         of each pair and tests it against tau - beta_ij.  Candidates leave through a wave prefix sum, ONE
+//                         global atomic per wave that has any, and 8-byte stores; the count runs on past the capacity.
+//   exact_kernel          one workgroup per 64 sorted candidates: the A and B row pieces are staged in LDS 128 k at a time
+//                         and wave 0 runs the k-ascending fmaf chains of mdx_rescore (lane = candidate).
+//   select_count/_write   the dense threshold compaction of an fp32 score matrix (one workgroup per row, ordered).
+//   the final order       one stable radix sort of (row, desc_key(score)) keys whose input is in (row, id) order, then a
+//                         gather and a binary search per row for the CSR offsets.
+#include <algorithm>
+
+#include <hipcub/hipcub.hpp>
+
+#include "mdx_common.h"
+
+namespace mdx {
+namespace {
+
+typedef float jn_f32x4 __attribute__((ext_vector_type(4)));
+typedef int jn_i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int JB_TILES = 8;                     // row tiles (of 16 rows) per block side: 128 rows
+constexpr int JB_ROWS = JB_TILES * 16;
+constexpr int J_GROUP = 16;                     // I blocks that run side by side over the J blocks (L2 reuse of both operands)
+constexpr double E_Q = 0.5 + 0x1p-15;           // E of the MDX_I8 bound
+constexpr float TINY = 0x1p-149f;               // floor of the factors: inf * factor is never NaN
+
+__device__ __forceinline__ float up_f32(double v)       // the smallest fp32 value >= v (v >= 0); +inf beyond the range
+{
+    float f = (float)v;
+    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
+    return f;
+}
+
+// ---------------------------------------------------------------- per-row factors
+
+__global__ __launch_bounds__(256) void join_stats_kernel(const jn_i32x4 *__restrict__ tiles, const float *__restrict__ scales, int64_t n,
+                                                         int64_t KB, const float *__restrict__ rows, int64_t ld, int64_t d,
+                                                         jn_f32x4 *__restrict__ stats)
+{
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;                                        // wave-uniform
+    double l1 = 0.0;
+    float a = 0.f;
+    int bad = 0;
+    for (int64_t k = lane; k < d; k += 64) {
+        const float x = rows[row * ld + k];
+        bad |= !__builtin_isfinite(x);
+        l1 += (double)fabsf(x);
+        a = fmaxf(a, fabsf(x));
+    }
+    // ||c||_1 from the row's codes: tile (row / 16, kb), lane (g, row % 16) holds 16 codes of k group g
+    const int64_t rt = row >> 4;
+    const int j = (int)(row & 15);
+    uint32_t c1 = 0;
+    for (int64_t kb = lane >> 2; kb < KB; kb += 16) {
+        const jn_i32x4 w = tiles[(rt * KB + kb) * 64 + (lane & 3) * 16 + j];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int c = (int)(int8_t)(uint8_t)((uint32_t)w[e >> 2] >> (8 * (e & 3)));
+            c1 += (uint32_t)(c < 0 ? -c : c);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        l1 += __shfl_xor(l1, o, 64);
+        a = fmaxf(a, __shfl_xor(a, o, 64));
+        bad |= __shfl_xor(bad, o, 64);
+        c1 += __shfl_xor(c1, o, 64);
+    }
+    if (lane != 0) return;
+    const float sc = scales[row];
+    // a zero row (a == 0) scores exactly 0; any other row needs a scale in [2^-106, 2^40] -- a nonzero row whose scale rounded
+    // to 0 (a subnormal max |x|) has scale c = 0 and an error of x itself, which no scale-proportional term covers
+    const bool covered = !bad && (a == 0.f || (sc >= 0x1p-106f && sc <= 0x1p40f));
+    jn_f32x4 st;
+    st[0] = sc;
+    if (covered) {
+        const double ud = (double)d * 0x1p-24, gamma = ud / (1.0 - ud);
+        // float64 rounding: ||x||_1 errs by at most d 2^-53 of itself, every other operation by 2^-53: (1 + (d + 16) 2^-52) covers it
+        const double slack = 1.0 + ((double)d + 16.0) * 0x1p-52;
+        st[1] = fmaxf(up_f32(E_Q * l1 * slack), TINY);                                   // q = E ||x||_1
+        st[2] = fmaxf(up_f32(E_Q * (double)sc * (double)c1 * slack), TINY);              // r = E scale ||c||_1
+        st[3] = fmaxf(up_f32(((double)sc + gamma * (double)a / E_Q) * slack), TINY);     // w = scale + gamma_d max|x| / E
+    } else {
+        st[1] = st[2] = st[3] = __builtin_inff();
+    }
+    stats[row] = st;
+}
+
+// ---------------------------------------------------------------- the join kernel
+
+// beta of x in the query role and y in the database role, rounded up (include/mdx.h): b >= beta + 2^-150
+__device__ __forceinline__ float beta_up(jn_f32x4 x, jn_f32x4 y, float c0)
+{
+    const float s = __fadd_rn(__fadd_rn(__fmul_rn(x[1], y[3]), __fmul_rn(y[2], fmaxf(x[0], TINY))), c0);
+    return __fmul_rn(s, 1.0f + 0x1p-20f);
+}
+
+// a: the A shard's tiles, b: B's (== a for the self-join).  A blocks [I0, I1) in groups of GS (<= J_GROUP) that sweep every J
+// block -- or, symmetric, one group of J_GROUP blocks from I0 against J >= I0.  out: (i << 32 | j) of every candidate, i, j
+// global rows of A and B.
+template <bool SYM>
+__global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
+                                                      const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
+                                                      int64_t I0, int64_t I1, int64_t NJ, int GS, float tau, float c0, uint64_t *__restrict__ out,
+                                                      int64_t capacity, unsigned long long *__restrict__ count)
+{
+    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // [buffer][A tiles, then B tiles][lane]: 2 x 16 KiB
+    int64_t I, J;
+    const int64_t bid = blockIdx.x;
+    if constexpr (SYM) {                                         // J >= I0; I = I0 + (0 .. J_GROUP-1), J >= I
+        I = I0 + bid % J_GROUP;
+        J = I0 + bid / J_GROUP;
+        if (I >= I1 || J < I) return;
+    } else {                                                     // groups of GS I blocks sweep every J block
+        const int64_t g = bid / (GS * NJ), w = bid % (GS * NJ);
+        I = I0 + g * GS + w % GS;
+        J = w / GS;
+        if (I >= I1) return;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wa = wave >> 1, wb = wave & 1;                     // the wave's 64 x 64 corner of the block
+
+    // stage loads: thread t moves pieces t, t + 256, t + 512, t + 768 of the 16 tiles (A 0..7, B 8..15) of a chunk
+    const jn_i32x4 *src[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int p = tid + 256 * u, t = p >> 6;
+        const int64_t rt = t < JB_TILES ? I * JB_TILES + t : J * JB_TILES + (t - JB_TILES);
+        src[u] = (t < JB_TILES ? a : b) + rt * KB * 64 + (p & 63);
+    }
+    jn_i32x4 reg[4];
+    auto fetch = [&](int kb) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) reg[u] = src[u][(int64_t)kb * 64];
+    };
+    auto put = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) lds[buf][tid + 256 * u] = reg[u];
+    };
+
+    jn_i32x4 acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = (jn_i32x4){0, 0, 0, 0};
+
+    fetch(0);
+    put(0);
+    __syncthreads();
+    for (int kb = 0; kb < KB; ++kb) {
+        const bool more = kb + 1 < KB;
+        if (more) fetch(kb + 1);                                 // in flight during the MFMAs
+        const jn_i32x4 *s = lds[kb & 1];
+        jn_i32x4 av[4], bv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) av[r] = s[(wa * 4 + r) * 64 + lane];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) bv[c] = s[(JB_TILES + wb * 4 + c) * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[r][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[r], bv[c], acc[r][c], 0, 0, 0);
+        if (more) {
+            put((kb + 1) & 1);                                   // every wave left this buffer before the last barrier
+            __syncthreads();
+        }
+    }
+
+    // Epilogue: lane (g, col) holds rows 4 g .. 4 g + 3 of A tile r against row col of B tile c
+    const int g4 = 4 * (lane >> 4), col = lane & 15;
+    int64_t jrow[4];
+    jn_f32x4 ys[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        jrow[c] = (J * JB_TILES + wb * 4 + c) * 16 + col;
+        ys[c] = jrow[c] < nb ? sb[jrow[c]] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    uint64_t mask = 0;                                           // bit (r * 4 + e) * 4 + c
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int64_t irow = (I * JB_TILES + wa * 4 + r) * 16 + g4 + e;
+            if (irow >= na) continue;
+            const jn_f32x4 xs = sa[irow];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (jrow[c] >= nb || (SYM && jrow[c] <= irow)) continue;
+                const float prod = __fmul_rn(ys[c][0], xs[0]);                  // scale_B * scale_A, as MDX_I8
+                const float sc = __fmul_rn((float)acc[r][c][e], prod);
+                float bnd = fminf(beta_up(xs, ys[c], c0), beta_up(ys[c], xs, c0));
+                if (xs[0] > 0.f && ys[c][0] > 0.f && prod < 0x1p-126f) bnd = __builtin_inff();   // the product may have underflowed
+                const float lhs = __fadd_rn(__fadd_rn(sc, __fmul_rn(fabsf(sc), 0x1p-21f)), bnd);
+                if (!(lhs < tau)) mask |= 1ull << ((r * 4 + e) * 4 + c);    // a NaN score is a candidate
+            }
+        }
+    }
+    const uint32_t mine = (uint32_t)__popcll(mask);
+    if (!__any(mine != 0)) return;
+    const uint32_t incl = wave_inclusive_sum(mine);
+    const uint32_t total = __shfl(incl, 63, 64);
+    unsigned long long base = 0;
+    if (lane == 63) base = atomicAdd(count, (unsigned long long)total);
+    base = __shfl(base, 63, 64);
+    int64_t pos = (int64_t)base + (incl - mine);
+    while (mask) {
+        const int bit = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        const int r = bit >> 4, e = (bit >> 2) & 3, c = bit & 3;
+        const int64_t irow = (I * JB_TILES + wa * 4 + r) * 16 + g4 + e;
+        if (pos < capacity) out[pos] = ((uint64_t)irow << 32) | (uint64_t)jrow[c];
+        ++pos;
+    }
+}
+
+// ---------------------------------------------------------------- exact stage
+
+constexpr int EX_TC = 64;              // candidates per workgroup: one per lane of wave 0
+constexpr int EX_KC = 128;             // k per stage
+constexpr int EX_LD = EX_KC + 4;
+
+__device__ __forceinline__ jn_f32x4 piece(const float *rows, int64_t id, int64_t ld, int64_t d, int64_t k, bool vec)
+{
+    jn_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (id < 0) return v;
+    const float *p = rows + id * ld;
+    if (vec && k + 4 <= d) return *(const jn_f32x4 *)(p + k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = k + e < d ? p[k + e] : 0.f;
+    return v;
+}
+
+// sorted candidates (i << 32 | j) -> key (i - m_lo) << 32 | desc_key(chain) for a hit, ~0 otherwise; idx = position
+__global__ __launch_bounds__(256) void exact_kernel(const float *__restrict__ ra, int64_t lda, const float *__restrict__ rb, int64_t ldb, int64_t d,
+                                                    const uint64_t *__restrict__ cand, int64_t P, float tau, int64_t m_lo, bool vec,
+                                                    float *__restrict__ score, uint64_t *__restrict__ key, int32_t *__restrict__ idx)
+{
+    __shared__ __attribute__((aligned(16))) float ta[EX_TC * EX_LD];
+    __shared__ __attribute__((aligned(16))) float tb[EX_TC * EX_LD];
+    const int64_t c0 = (int64_t)blockIdx.x * EX_TC;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l32 = lane & 31;
+    // wave w stages candidates 16 w .. 16 w + 15: two rows per wave-instruction (32 lanes x 16 B = one 512-B piece)
+    int64_t ia[8], ib[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int64_t p = c0 + wave * 16 + 2 * u + half;
+        const uint64_t kk = p < P ? cand[p] : ~0ull;
+        ia[u] = p < P ? (int64_t)(kk >> 32) : -1;
+        ib[u] = p < P ? (int64_t)(kk & 0xFFFFFFFFu) : -1;
+    }
+    const int64_t d_pad = (d + 63) / 64 * 64;
+    const int64_t stages = (d_pad + EX_KC - 1) / EX_KC;
+    jn_f32x4 ra_[8], rb_[8];
+    auto fetch = [&](int64_t k0) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            ra_[u] = piece(ra, ia[u], lda, d, k0 + 4 * l32, vec);
+            rb_[u] = piece(rb, ib[u], ldb, d, k0 + 4 * l32, vec);
+        }
+    };
+    auto put = [&]() {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int c = wave * 16 + 2 * u + half;
+            *(jn_f32x4 *)(ta + c * EX_LD + 4 * l32) = ra_[u];
+            *(jn_f32x4 *)(tb + c * EX_LD + 4 * l32) = rb_[u];
+        }
+    };
+    float acc = 0.f;
+    fetch(0);
+    put();
+    __syncthreads();
+    for (int64_t s = 0; s < stages; ++s) {
+        const int64_t k0 = s * EX_KC;
+        if (s + 1 < stages) fetch(k0 + EX_KC);
+        if (wave == 0) {
+            const int kend = (int)(d_pad - k0 < EX_KC ? d_pad - k0 : EX_KC);     // a multiple of 64
+            const float *x = ta + lane * EX_LD, *y = tb + lane * EX_LD;
+            for (int kk = 0; kk < kend; kk += 4) {
+                const jn_f32x4 xv = *(const jn_f32x4 *)(x + kk);
+                const jn_f32x4 yv = *(const jn_f32x4 *)(y + kk);
+                acc = __builtin_fmaf(xv[0], yv[0], acc);
+                acc = __builtin_fmaf(xv[1], yv[1], acc);
+                acc = __builtin_fmaf(xv[2], yv[2], acc);
+                acc = __builtin_fmaf(xv[3], yv[3], acc);
+            }
+        }
+        if (s + 1 < stages) {
+            __syncthreads();
+            put();
+            __syncthreads();
+        }
+    }
+    const int64_t p = c0 + lane;
+    if (wave == 0 && p < P) {
+        const uint64_t kk = cand[p];
+        const bool hit = acc >= tau;                             // NaN: never a hit
+        score[p] = acc;
+        key[p] = hit ? ((uint64_t)((int64_t)(kk >> 32) - m_lo) << 32) | desc_key(acc) : ~0ull;
+        idx[p] = (int32_t)p;
+    }
+}
+
+// ---------------------------------------------------------------- dense compaction
+
+// hits of row r of scores [m, n] at ld: s >= tau and (diag < 0 or j > diag + r)
+__device__ __forceinline__ bool dense_hit(float s, int64_t j, int64_t r, int64_t diag, float tau)
+{
+    return s >= tau && (diag < 0 || j > diag + r);
+}
+
+__global__ __launch_bounds__(256) void select_count_kernel(const float *__restrict__ sc, int64_t n, int64_t ld, int64_t diag, float tau,
+                                                           int64_t *__restrict__ counts)
+{
+    __shared__ int64_t part[4];
+    const int64_t r = blockIdx.x;
+    int64_t c = 0;
+    for (int64_t j = threadIdx.x; j < n; j += 256) c += dense_hit(sc[r * ld + j], j, r, diag, tau);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[r] = part[0] + part[1] + part[2] + part[3];
+}
+
+// row r's hits in ascending j at offsets[r]: key (r << 32 | desc_key), idx = position, the ids and scores beside
+__global__ __launch_bounds__(256) void select_write_kernel(const float *__restrict__ sc, int64_t n, int64_t ld, int64_t diag, float tau,
+                                                           const int64_t *__restrict__ offsets, int64_t m, int64_t capacity,
+                                                           uint64_t *__restrict__ key, int32_t *__restrict__ idx, int64_t *__restrict__ ids,
+                                                           float *__restrict__ vals)
+{
+    __shared__ uint32_t wsum[4];
+    if (offsets[m] > capacity) return;                           // the caller retries with the size offsets[m]
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t pos = offsets[r];
+    for (int64_t j0 = 0; j0 < n; j0 += 256) {
+        const int64_t j = j0 + tid;
+        const float s = j < n ? sc[r * ld + j] : 0.f;
+        const bool hit = j < n && dense_hit(s, j, r, diag, tau);
+        const uint32_t incl = wave_inclusive_sum(hit ? 1u : 0u);
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            before += w < wave ? wsum[w] : 0u;
+            total += wsum[w];
+        }
+        if (hit) {
+            const int64_t p = pos + before + incl - 1;
+            key[p] = ((uint64_t)r << 32) | desc_key(s);
+            idx[p] = (int32_t)p;
+            ids[p] = j;
+            vals[p] = s;
+        }
+        pos += total;
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- the final order
+
+__global__ __launch_bounds__(256) void fill_kernel(uint64_t *__restrict__ key, int32_t *__restrict__ idx, int64_t P)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < P) {
+        key[p] = ~0ull;
+        idx[p] = (int32_t)p;
+    }
+}
+
+// out[p] = the hit at sorted position p (j from the candidate key or from ids_in; score from vals)
+__global__ __launch_bounds__(256) void gather_kernel(const uint64_t *__restrict__ key, const int32_t *__restrict__ idx, int64_t P,
+                                                     const uint64_t *__restrict__ cand, const int64_t *__restrict__ ids_in,
+                                                     const float *__restrict__ vals, int64_t *__restrict__ out_ids, float *__restrict__ out_scores)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P || key[p] == ~0ull) return;
+    const int32_t q = idx[p];
+    out_ids[p] = cand ? (int64_t)(cand[q] & 0xFFFFFFFFu) : ids_in[q];
+    out_scores[p] = vals[q];
+}
+
+// offsets[r] = the first sorted position whose row is >= r (non-hits, key ~0, sort last)
+__global__ __launch_bounds__(256) void offsets_kernel(const uint64_t *__restrict__ key, int64_t P, int64_t m, int64_t *__restrict__ offsets)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r > m) return;
+    int64_t lo = 0, hi = P;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)(key[mid] >> 32) < r && key[mid] != ~0ull) lo = mid + 1;
+        else hi = mid;
+    }
+    offsets[r] = lo;
+}
+
+int key_bits(int64_t m)                 // bits of the row field that keep ~0 (non-hits) above every row < m
+{
+    int b = 1;
+    while (b < 32 && (1ll << b) - 1 <= m) ++b;
+    return 32 + b;
+}
+
+struct Carve {
+    char *p;
+    int64_t used = 0;
+    template <class T> T *take(int64_t count)
+    {
+        T *r = (T *)(p ? p + used : nullptr);
+        used += round_up(count * (int64_t)sizeof(T), 256);
+        return r;
+    }
+};
+
+// the stable sort of (key, idx) over P items: temp bytes (query with tmp == nullptr)
+size_t sort_bytes(int64_t P, int end_bit)
+{
+    size_t t = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const int32_t *)nullptr,
+                                             (int32_t *)nullptr, (int)P, 0, end_bit, (hipStream_t)0);
+    return t;
+}
+
+size_t cand_sort_bytes(int64_t P, int end_bit)
+{
+    size_t t = 0;
+    (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)P, 0, end_bit, (hipStream_t)0);
+    return t;
+}
+
+size_t scan_bytes(int64_t m)
+{
+    size_t t = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const int64_t *)nullptr, (int64_t *)nullptr, (int)(m + 1), (hipStream_t)0);
+    return t;
+}
+
+int64_t resolve_layout(int64_t P, int64_t m, Carve &cv, uint64_t **cs, float **score, uint64_t **key, int32_t **idx, uint64_t **key2,
+                       int32_t **idx2, void **tmp, size_t *tmp_bytes)
+{
+    *cs = cv.take<uint64_t>(P);
+    *score = cv.take<float>(P);
+    *key = cv.take<uint64_t>(P);
+    *idx = cv.take<int32_t>(P);
+    *key2 = cv.take<uint64_t>(P);
+    *idx2 = cv.take<int32_t>(P);
+    const size_t t = std::max(sort_bytes(P, key_bits(m)), cand_sort_bytes(P, 64));
+    *tmp_bytes = t;
+    *tmp = cv.take<char>((int64_t)t);
+    return cv.used;
+}
+
+int64_t select_layout(int64_t m, int64_t capacity, Carve &cv, int64_t **counts, uint64_t **key, int32_t **idx, uint64_t **key2,
+                      int32_t **idx2, int64_t **ids, float **vals, void **tmp, size_t *tmp_bytes)
+{
+    const int64_t P = capacity > 0 ? capacity : 1;
+    *counts = cv.take<int64_t>(m + 1);
+    *key = cv.take<uint64_t>(P);
+    *idx = cv.take<int32_t>(P);
+    *key2 = cv.take<uint64_t>(P);
+    *idx2 = cv.take<int32_t>(P);
+    *ids = cv.take<int64_t>(P);
+    *vals = cv.take<float>(P);
+    const size_t t = std::max(sort_bytes(P, key_bits(m)), scan_bytes(m));
+    *tmp_bytes = t;
+    *tmp = cv.take<char>((int64_t)t);
+    return cv.used;
+}
+
+constexpr int64_t J_MAX_ITEMS = (1ll << 31) - 1;     // hipcub item counts and the int32 positions of the sort
+
+__global__ __launch_bounds__(256) void center_kernel(const float *__restrict__ src, int64_t n, int64_t d, int layout,
+                                                     const float *__restrict__ center, float *__restrict__ out)
+{
+    const int64_t total = n * d;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t row = e / d, k = e % d;
+        const float x = layout == MDX_ROW_MAJOR ? src[e] : src[k * n + row];
+        out[e] = center ? x - center[k] : x;
+    }
+}
+
+}  // namespace
+}  // namespace mdx
+
+using namespace mdx;
+
+extern "C" {
+
+int mdx_center_rows(const float *src, int64_t n, int64_t d, int layout, const float *center, float *out, void *stream)
+{
+    MDX_CHECK_ARG(src && out, "mdx_center_rows: NULL pointer");
+    MDX_CHECK_ARG(n >= 1 && d >= 1, "mdx_center_rows: n=%lld d=%lld must be >= 1", (long long)n, (long long)d);
+    MDX_CHECK_ARG(layout == MDX_DIM_MAJOR || layout == MDX_ROW_MAJOR, "mdx_center_rows: layout %d", layout);
+    const int64_t blocks = std::min(ceil_div(n * d, (int64_t)256), (int64_t)65536);
+    hipLaunchKernelGGL(center_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, n, d, layout, center, out);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int mdx_join_stats(const mdx_index *index, const float *rows, int64_t ld, float *stats, void *stream)
+{
+    MDX_CHECK_ARG(index && rows && stats, "mdx_join_stats: NULL pointer");
+    const void *tiles = nullptr;
+    const float *scales = nullptr;
+    int64_t n = 0, RT = 0, KB = 0, d = 0;
+    MDX_CHECK_ARG(i8_view(index, &tiles, &scales, &n, &RT, &KB), "mdx_join_stats: an int8 shard is needed (an fp16 or fp32 one has no bound)");
+    MDX_CHECK_ARG(mdx_index_info(index, nullptr, &d, nullptr, nullptr) == MDX_OK, "mdx_join_stats: index info");
+    MDX_CHECK_ARG(ld >= d, "mdx_join_stats: ld=%lld < d=%lld", (long long)ld, (long long)d);
+    MDX_CHECK_ARG(ceil_div(n, (int64_t)4) < (1ll << 31), "mdx_join_stats: shard too large for one launch");
+    hipLaunchKernelGGL(join_stats_kernel, dim3((unsigned)ceil_div(n, (int64_t)4)), dim3(256), 0, (hipStream_t)stream, (const jn_i32x4 *)tiles,
+                       scales, n, KB, rows, ld, d, (jn_f32x4 *)stats);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int mdx_join_candidates(const mdx_index *a, const float *stats_a, const mdx_index *b, const float *stats_b, int64_t a_lo, int64_t a_hi,
+                        int symmetric, float tau, uint64_t *pairs, int64_t capacity, int64_t *count, void *stream)
+{
+    MDX_CHECK_ARG(a && stats_a && b && stats_b && pairs && count, "mdx_join_candidates: NULL pointer");
+    MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_join_candidates: tau must be finite");
+    MDX_CHECK_ARG(capacity >= 0, "mdx_join_candidates: capacity=%lld < 0", (long long)capacity);
+    MDX_CHECK_ARG(!symmetric || a == b, "mdx_join_candidates: the self-join needs a == b");
+    const void *ta = nullptr, *tb = nullptr;
+    const float *sca = nullptr, *scb = nullptr;
+    int64_t na = 0, rta = 0, kba = 0, nb = 0, rtb = 0, kbb = 0, da = 0, db = 0;
+    MDX_CHECK_ARG(i8_view(a, &ta, &sca, &na, &rta, &kba) && i8_view(b, &tb, &scb, &nb, &rtb, &kbb),
+                  "mdx_join_candidates: int8 shards are needed (an fp16 or fp32 one has no bound)");
+    (void)mdx_index_info(a, nullptr, &da, nullptr, nullptr);
+    (void)mdx_index_info(b, nullptr, &db, nullptr, nullptr);
+    MDX_CHECK_ARG(da == db, "mdx_join_candidates: dimensions %lld and %lld differ", (long long)da, (long long)db);
+    MDX_CHECK_ARG(na < (1ll << 31) && nb < (1ll << 31), "mdx_join_candidates: n >= 2^31");
+    MDX_CHECK_ARG(a_lo >= 0 && a_lo < a_hi && a_hi <= na && a_lo % JB_ROWS == 0,
+                  "mdx_join_candidates: rows [%lld, %lld) of A: 0 <= lo < hi <= n=%lld and lo a multiple of %d", (long long)a_lo, (long long)a_hi,
+                  (long long)na, JB_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    MDX_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
+    const int64_t I0 = a_lo / JB_ROWS, I1 = ceil_div(a_hi, (int64_t)JB_ROWS), NJ = ceil_div(nb, (int64_t)JB_ROWS);
+    const float c0 = (float)((double)(da + 2) * 0x1p-149);      // exact: a multiple of 2^-149 below 2^-126
+    if (symmetric) {
+        for (int64_t g = I0; g < I1; g += J_GROUP) {             // one launch per group of J_GROUP I blocks: J >= g only
+            const int64_t blocks = J_GROUP * (NJ - g);
+            MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
+            hipLaunchKernelGGL(join_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
+                               (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, g, std::min(g + J_GROUP, I1), NJ, J_GROUP, tau, c0,
+                               pairs, capacity, (unsigned long long *)count);
+        }
+    } else {
+        const int64_t gs = std::min(I1 - I0, (int64_t)J_GROUP);    // a range search of <= 128 queries is one block row
+        const int64_t blocks = ceil_div(I1 - I0, gs) * gs * NJ;
+        MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
+        hipLaunchKernelGGL(join_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
+                           (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, I0, I1, NJ, (int)gs, tau, c0, pairs, capacity,
+                           (unsigned long long *)count);
+    }
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int64_t mdx_join_resolve_workspace(int64_t P, int64_t m)
+{
+    if (P < 1 || m < 1 || P > J_MAX_ITEMS || m > J_MAX_ITEMS) return 0;
+    Carve cv{nullptr};
+    uint64_t *cs, *key, *key2;
+    int32_t *idx, *idx2;
+    float *score;
+    void *tmp;
+    size_t tb;
+    return resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb) + 256;
+}
+
+int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs, int64_t P,
+                     float tau, int64_t m_lo, int64_t m, int64_t *offsets, int64_t *ids, float *scores, void *workspace, int64_t workspace_bytes,
+                     void *stream)
+{
+    MDX_CHECK_ARG(rows_a && rows_b && pairs && offsets && ids && scores, "mdx_join_resolve: NULL pointer");
+    MDX_CHECK_ARG(P >= 1 && m >= 1 && d >= 1, "mdx_join_resolve: P=%lld m=%lld d=%lld must be >= 1", (long long)P, (long long)m, (long long)d);
+    MDX_CHECK_ARG(P <= J_MAX_ITEMS && m <= J_MAX_ITEMS, "mdx_join_resolve: P=%lld or m=%lld >= 2^31", (long long)P, (long long)m);
+    MDX_CHECK_ARG(lda >= d && ldb >= d, "mdx_join_resolve: lda=%lld / ldb=%lld < d=%lld", (long long)lda, (long long)ldb, (long long)d);
+    MDX_CHECK_ARG(m_lo >= 0, "mdx_join_resolve: m_lo=%lld < 0", (long long)m_lo);
+    MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_join_resolve: tau must be finite");
+    const int64_t need = mdx_join_resolve_workspace(P, m);
+    if (!workspace || workspace_bytes < need) {
+        set_error("mdx_join_resolve: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};     // the + 256 of the size covers the alignment
+    uint64_t *cs, *key, *key2;
+    int32_t *idx, *idx2;
+    float *score;
+    void *tmp;
+    size_t tb;
+    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)ceil_div(P, (int64_t)256);
+    // candidates in (i, j) order: the chains then run row-grouped, and the stable sort below breaks ties by ascending j
+    MDX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tb, pairs, cs, (int)P, 0, 64, s));
+    const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
+    hipLaunchKernelGGL(exact_kernel, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
+                       (const uint64_t *)cs, P, tau, m_lo, vec, score, key, idx);
+    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
+    hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(256), 0, s, (const uint64_t *)key2, (const int32_t *)idx2, P, (const uint64_t *)cs,
+                       (const int64_t *)nullptr, (const float *)score, ids, scores);
+    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, P, m, offsets);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int64_t mdx_range_select_workspace(int64_t m, int64_t capacity)
+{
+    if (m < 1 || capacity < 0 || m > J_MAX_ITEMS || capacity > J_MAX_ITEMS) return 0;
+    Carve cv{nullptr};
+    int64_t *counts, *ids;
+    uint64_t *key, *key2;
+    int32_t *idx, *idx2;
+    float *vals;
+    void *tmp;
+    size_t tb;
+    return select_layout(m, capacity, cv, &counts, &key, &idx, &key2, &idx2, &ids, &vals, &tmp, &tb) + 256;
+}
+
+int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, float tau, int64_t diag, int64_t *offsets, int64_t *ids,
+                     float *out_scores, int64_t capacity, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    MDX_CHECK_ARG(scores && offsets && ids && out_scores, "mdx_range_select: NULL pointer");
+    MDX_CHECK_ARG(m >= 1 && n >= 1, "mdx_range_select: m=%lld n=%lld must be >= 1", (long long)m, (long long)n);
+    MDX_CHECK_ARG(m <= J_MAX_ITEMS && capacity <= J_MAX_ITEMS, "mdx_range_select: m=%lld or capacity=%lld >= 2^31", (long long)m,
+                  (long long)capacity);
+    MDX_CHECK_ARG(ld >= n, "mdx_range_select: ld=%lld < n=%lld", (long long)ld, (long long)n);
+    MDX_CHECK_ARG(capacity >= 0, "mdx_range_select: capacity=%lld < 0", (long long)capacity);
+    MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_range_select: tau must be finite");
+    const int64_t need = mdx_range_select_workspace(m, capacity);
+    if (!workspace || workspace_bytes < need) {
+        set_error("mdx_range_select: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};
+    int64_t *counts, *hid;
+    uint64_t *key, *key2;
+    int32_t *idx, *idx2;
+    float *vals;
+    void *tmp;
+    size_t tb;
+    select_layout(m, capacity, cv, &counts, &key, &idx, &key2, &idx2, &hid, &vals, &tmp, &tb);
+    const int64_t P = capacity > 0 ? capacity : 1;
+    hipStream_t s = (hipStream_t)stream;
+    MDX_HIP(hipMemsetAsync(counts + m, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)m), dim3(256), 0, s, scores, n, ld, diag, tau, counts);
+    MDX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)counts, offsets, (int)(m + 1), s));
+    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, key, idx, P);
+    hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)m), dim3(256), 0, s, scores, n, ld, diag, tau, (const int64_t *)offsets, m, capacity,
+                       key, idx, hid, vals);
+    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, (const int32_t *)idx2, P,
+                       (const uint64_t *)nullptr, (const int64_t *)hid, (const float *)vals, ids, out_scores);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+}  // extern "C"

@@ -705,6 +705,156 @@ def rescore_certify(scores, t, queries, bounds, n, qlayout="ND", center=None):
     return depth, upper
 
 
+# ------------------------------------------------------------- range search and self-join
+
+JOIN_BLOCK = 128                  # include/mdx.h MDX_JOIN_BLOCK: rows per block side of the join kernel
+_MAX_ITEMS = (1 << 31) - 1        # pairs, rows and capacities of one call stay below 2^31
+
+
+def _tau(threshold):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not math.isfinite(threshold):
+        raise ValueError("threshold must be a finite number, got %r" % (threshold,))
+    with np.errstate(over="ignore"):
+        t = float(np.float32(threshold))
+    if not math.isfinite(t):
+        raise ValueError("threshold %r is outside the fp32 range" % (threshold,))
+    return t
+
+
+def center_rows(queries, qlayout="ND", center=None):
+    """fp32 ``[nq, d]`` row-major: ``queries - center`` (one fp32 subtraction per element; a copy without ``center``) --
+    the query rows ``x_q`` of a range search (``mdx_center_rows``)."""
+    qp = _dev(queries, torch.float32, "queries")
+    nq, d, lay = _layout(queries, qlayout, "queries")
+    if nq < 1 or d < 1:
+        raise ValueError("queries must be non-empty, got %d x %d" % (nq, d))
+    cp = _dev(center, torch.float32, "center") if center is not None else None
+    if center is not None and center.numel() != d:
+        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    out = torch.empty((nq, d), dtype=torch.float32, device=queries.device)
+    with _on(queries):
+        check(_lib.lib().mdx_center_rows(qp, nq, d, lay, cp, _vp(out.data_ptr()), _stream()), "mdx_center_rows")
+    return out
+
+
+def join_stats(index, rows):
+    """fp32 ``[n, 4]``: the per-row factors ``{p, q, r, w}`` of the pruning bound (``mdx_join_stats``, include/mdx.h) of an int8
+    ``index`` and the fp32 rows ``[n, d]`` it was built from (rows contiguous, any stride)."""
+    if not isinstance(index, DescriptorIndex) or index._h is None:
+        raise ValueError("join_stats: an open DescriptorIndex is needed")
+    if index.storage != "i8":
+        raise ValueError("join_stats: pruning needs an int8 index (an %s one has no bound)" % index.storage)
+    rp, ld = _rows(rows, "rows")
+    if tuple(rows.shape) != (index.n, index.d):
+        raise ValueError("rows must be the index's [%d, %d] rows, got %s" % (index.n, index.d, tuple(rows.shape)))
+    stats = torch.empty((index.n, 4), dtype=torch.float32, device=rows.device)
+    with _on(rows):
+        check(_lib.lib().mdx_join_stats(index._h, rp, ld, _vp(stats.data_ptr()), _stream()), "mdx_join_stats")
+    return stats
+
+
+def join_candidates(a, stats_a, b, stats_b, threshold, a_lo=0, a_hi=None, symmetric=False, capacity=1 << 20):
+    """``(pairs uint64-as-int64 [min(count, capacity)], count)``: the candidates ``i << 32 | j`` of the join kernel
+    (``mdx_join_candidates``) for rows ``[a_lo, a_hi)`` of int8 index ``a`` against every row of ``b`` (``symmetric``: a is b,
+    j > i).  ``count`` may exceed ``capacity``: then call again with ``capacity >= count``.  Synchronises the stream (reads
+    the count)."""
+    tau = _tau(threshold)
+    for name, ix in (("a", a), ("b", b)):
+        if not isinstance(ix, DescriptorIndex) or ix._h is None:
+            raise ValueError("join_candidates: %s must be an open DescriptorIndex" % name)
+        if ix.storage != "i8":
+            raise ValueError("join_candidates: pruning needs int8 indexes (%s is %s)" % (name, ix.storage))
+    if a.d != b.d:
+        raise ValueError("join_candidates: dimensions %d and %d differ" % (a.d, b.d))
+    if symmetric and a is not b:
+        raise ValueError("join_candidates: the self-join joins one index with itself")
+    a_hi = a.n if a_hi is None else int(a_hi)
+    a_lo = int(a_lo)
+    if not (0 <= a_lo < a_hi <= a.n) or a_lo % JOIN_BLOCK:
+        raise ValueError("join_candidates: rows [%d, %d) of %d, the first a multiple of %d" % (a_lo, a_hi, a.n, JOIN_BLOCK))
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= _MAX_ITEMS:
+        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
+    for name, st, ix in (("stats_a", stats_a, a), ("stats_b", stats_b, b)):
+        _dev(st, torch.float32, name)
+        if tuple(st.shape) != (ix.n, 4):
+            raise ValueError("%s must be join_stats of its index: [%d, 4]" % (name, ix.n))
+    pairs = torch.empty(max(capacity, 1), dtype=torch.int64, device=a.device)
+    count = torch.zeros(1, dtype=torch.int64, device=a.device)
+    with _on(pairs):
+        check(_lib.lib().mdx_join_candidates(a._h, _vp(stats_a.data_ptr()), b._h, _vp(stats_b.data_ptr()), a_lo, a_hi, int(bool(symmetric)),
+                                             tau, _vp(pairs.data_ptr()), capacity, _vp(count.data_ptr()), _stream()), "mdx_join_candidates")
+    c = int(count.item())
+    return pairs[:min(c, capacity)], c
+
+
+def join_resolve(rows_a, rows_b, pairs, threshold, m_lo, m):
+    """``(offsets int64 [m + 1], ids int64 [hits], scores fp32 [hits])``: the exact chains of the candidate ``pairs`` (int64
+    ``i << 32 | j``, unique, rows i in ``[m_lo, m_lo + m)``) of ``rows_a`` x ``rows_b``, the hits ``>= threshold`` and their CSR
+    over rows ``m_lo ..`` in rank order (``mdx_join_resolve``).  Synchronises the stream (reads the hits)."""
+    tau = _tau(threshold)
+    ap, lda = _rows(rows_a, "rows_a")
+    bp, ldb = _rows(rows_b, "rows_b")
+    if rows_a.shape[1] != rows_b.shape[1]:
+        raise ValueError("rows_a and rows_b differ in dimension")
+    d = rows_a.shape[1]
+    m, m_lo = int(m), int(m_lo)
+    if m < 1 or m_lo < 0 or m > _MAX_ITEMS:
+        raise ValueError("join_resolve: m=%d must be in [1, 2^31) and m_lo=%d >= 0" % (m, m_lo))
+    dev = rows_a.device
+    P = pairs.numel()
+    if P == 0:
+        return (torch.zeros(m + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty(0, dtype=torch.float32, device=dev))
+    _dev(pairs, torch.int64, "pairs")
+    if P > _MAX_ITEMS:
+        raise ValueError("join_resolve: %d pairs, at most 2^31 - 1 per call" % P)
+    h = _lib.lib()
+    need = h.mdx_join_resolve_workspace(P, m)
+    ws = _workspace(need, dev)
+    offsets = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    ids = torch.empty(P, dtype=torch.int64, device=dev)
+    scores = torch.empty(P, dtype=torch.float32, device=dev)
+    with _on(rows_a):
+        check(h.mdx_join_resolve(ap, lda, bp, ldb, d, _vp(pairs.data_ptr()), P, tau, m_lo, m, _vp(offsets.data_ptr()),
+                                 _vp(ids.data_ptr()), _vp(scores.data_ptr()), _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_join_resolve")
+    hits = int(offsets[m].item())
+    return offsets, ids[:hits], scores[:hits]
+
+
+def range_select(scores, threshold, diag=None, capacity=None):
+    """``(offsets int64 [m + 1], ids int64 [hits], scores fp32 [hits])``: the deterministic threshold compaction of an fp32 score
+    matrix ``[m, n]`` (rows contiguous, any stride) into the CSR of include/mdx.h (``mdx_range_select``): hits ``s >= threshold``,
+    for ``diag`` not None only ``j > diag + r`` in row r (the upper triangle of a self-join block whose first row is ``diag``).
+    Synchronises the stream; with ``capacity`` too small for the hits it runs again at their exact number."""
+    tau = _tau(threshold)
+    sp, ld = _rows(scores, "scores")
+    m, n = scores.shape
+    if m < 1 or n < 1 or m > _MAX_ITEMS:
+        raise ValueError("range_select: scores must be non-empty, got %d x %d" % (m, n))
+    if diag is not None and (isinstance(diag, bool) or not isinstance(diag, int) or diag < 0):
+        raise ValueError("diag must be None or an integer >= 0, got %r" % (diag,))
+    cap = 1 << 16 if capacity is None else capacity
+    if isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap <= _MAX_ITEMS:
+        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
+    h = _lib.lib()
+    dev = scores.device
+    offsets = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    while True:
+        need = h.mdx_range_select_workspace(m, cap)
+        ws = _workspace(need, dev)
+        ids = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        vals = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+        with _on(scores):
+            check(h.mdx_range_select(sp, m, n, ld, tau, -1 if diag is None else int(diag), _vp(offsets.data_ptr()), _vp(ids.data_ptr()),
+                                     _vp(vals.data_ptr()), cap, _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_range_select")
+        hits = int(offsets[m].item())
+        if hits <= cap:
+            return offsets, ids[:hits], vals[:hits]
+        if hits > _MAX_ITEMS:
+            raise ValueError("range_select: %d hits, more than one call holds (2^31 - 1)" % hits)
+        cap = hits
+
+
 def _rows(t, what):
     """(pointer, row stride) of a 2-D fp32 CUDA matrix whose rows are contiguous (a row slice of a larger matrix is fine)."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:

@@ -12,12 +12,22 @@ is provably the exact fp32 top-k, bit for bit (``include/mdx.h`` states the proo
 certificate.  With ``exact=True``, every query whose certified depth is below k (every query of an fp16 index) is run
 again through the exact path, ``scores_rowmajor`` + ``topk``, on those queries only; then every row of the result equals
 ``topk(scores_rowmajor(rows, queries), k)``.
+
+``range_search(index, rows, queries, threshold)`` and ``self_join(index, rows, threshold)`` return EVERY pair whose exact fp32
+chain score is ``>= threshold`` -- query x database row, or database row pairs i < j -- as a CSR :data:`RangeResult`.  With an
+int8 ``index`` the join kernel prunes on the int8 scores with a per-pair error bound that can only over-select (the proof is in
+``include/mdx.h``), and the exact chain decides every candidate; with ``index=None`` the exact route scores everything in fp32 and
+compacts.  Both routes return the same bits.
 """
 from collections import namedtuple
 
 import torch
 
 from . import ops
+
+RangeResult = namedtuple("RangeResult", ["offsets", "ids", "scores"])
+RangeResult.__doc__ = """CSR over the queries (the rows i of a self-join): offsets int64 [m + 1], ids int64 [P], scores fp32 [P]; segment q
+= ``ids[offsets[q]:offsets[q + 1]]``, larger score first, equal scores by ascending id."""
 
 SearchResult = namedtuple("SearchResult", ["ids", "scores", "certified", "fallback"])
 SearchResult.__doc__ = """ids int64 [nq, k], scores fp32 [nq, k]; certified int32 [nq] (int8 index) or None (fp16);
@@ -68,3 +78,135 @@ def search(index, rows, queries, k, shortlist, qlayout="ND", center=None, exact=
             ids[fallback] = fi
             sc[fallback] = fs
     return SearchResult(ids, sc, certified, fallback)
+
+
+def _check_rows(index, rows):
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.float32 or rows.dim() != 2:
+        raise ValueError("rows must be a 2-d fp32 device tensor [N, D]")
+    if rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("rows must be non-empty, got %s" % (tuple(rows.shape),))
+    if index is not None:
+        if not isinstance(index, ops.DescriptorIndex):
+            raise ValueError("index must be an int8 DescriptorIndex of rows, or None (the exact route)")
+        if index.storage != "i8":
+            raise ValueError("pruning needs an int8 index; this one is stored as %s (pass index=None for the exact route)" % index.storage)
+        if tuple(rows.shape) != (index.n, index.d):
+            raise ValueError("rows must be the index's [%d, %d] rows, got %s" % (index.n, index.d, tuple(rows.shape)))
+
+
+def _join_stats(index, rows):
+    """The index's join_stats for these rows, reduced once and kept on the index."""
+    key = (rows.data_ptr(), tuple(rows.shape), tuple(rows.stride()))
+    cached = getattr(index, "_join_stats", None)
+    if cached is None or cached[0] != key:
+        cached = (key, ops.join_stats(index, rows))
+        index._join_stats = cached
+    return cached[1]
+
+
+def _candidates(a, sa, b, sb, tau, lo, hi, symmetric, capacity, remedy):
+    pairs, count = ops.join_candidates(a, sa, b, sb, tau, lo, hi, symmetric, capacity)
+    if count > capacity:                                   # the kernel counted on: run again at the exact size
+        if count > ops._MAX_ITEMS:
+            raise ValueError("%d candidates, more than one call holds (2^31 - 1): %s" % (count, remedy))
+        pairs, count = ops.join_candidates(a, sa, b, sb, tau, lo, hi, symmetric, count)
+    return pairs
+
+
+def _concat(parts, device):
+    """One CSR from consecutive row blocks' CSRs."""
+    if len(parts) == 1:
+        return RangeResult(*parts[0])
+    offs, base = [torch.zeros(1, dtype=torch.int64, device=device)], 0
+    for o, ids, _ in parts:
+        offs.append(o[1:] + base)
+        base += ids.numel()
+    return RangeResult(torch.cat(offs), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]))
+
+
+def range_search(index, rows, queries, threshold, qlayout="ND", center=None):
+    """Every database row whose exact fp32 chain score against ``queries`` (minus ``center``) is ``>= threshold``, as a
+    :data:`RangeResult` over the queries.  ``rows`` fp32 ``[N, D]`` on the device; ``index`` an int8 ``DescriptorIndex`` of
+    ``rows`` (pruned on the int8 shard) or None (the exact route: ``scores_rowmajor``, or an fp32 index where D % 4 != 0, then
+    :func:`ops.range_select`).  Both give the bits of ``mdx_scores`` on an fp32 index, filtered and in rank order."""
+    _check_rows(index, rows)
+    tau = ops._tau(threshold)
+    x = ops.center_rows(queries, qlayout, center)             # x_q = q - center, row-major
+    nq, d = x.shape
+    if d != rows.shape[1]:
+        raise ValueError("query dimension %d != rows dimension %d" % (d, rows.shape[1]))
+    if index is None:                                         # blocks of queries: ~256 MB of fp32 scores at a time
+        n = rows.shape[0]
+        block = max(1, (1 << 28) // (4 * n))
+        fp32 = None if d % 4 == 0 else ops.DescriptorIndex(rows, "ND")
+        try:
+            parts = []
+            for lo in range(0, nq, block):
+                sub = x[lo:min(nq, lo + block)]
+                sc = ops.scores_rowmajor(rows, sub, "ND") if fp32 is None else fp32.scores(sub, "ND")
+                parts.append(ops.range_select(sc, tau))
+                del sc
+            return _concat(parts, rows.device)
+        finally:
+            if fp32 is not None:
+                fp32.close()
+    qix = ops.DescriptorIndex(x, "ND", storage="i8")
+    try:
+        pairs = _candidates(qix, ops.join_stats(qix, x), index, _join_stats(index, rows), tau, 0, nq, False, max(4096, 64 * nq),
+                            "search fewer queries at a time")
+        return RangeResult(*ops.join_resolve(x, rows, pairs, tau, 0, nq))
+    finally:
+        qix.close()
+
+
+def self_join(index, rows, threshold, chunk=None, max_pairs=None):
+    """Every pair i < j of ``rows`` (fp32 ``[N, D]`` on the device) whose exact fp32 chain score is ``>= threshold``, as a
+    :data:`RangeResult` over i.  ``index``: an int8 ``DescriptorIndex`` of ``rows`` (the join kernel prunes, the exact chain
+    decides) or None (the exact route: fp32 scores of row blocks against every row, then :func:`ops.range_select`).  Memory is
+    bounded by blocks of ``chunk`` rows (a multiple of 128 on the pruned route); a chunk whose candidates overflow the buffer is
+    run again at their exact number.  ``max_pairs``: raise ValueError as soon as the result holds more pairs.  The bits depend
+    on neither ``chunk`` nor the buffer sizes."""
+    _check_rows(index, rows)
+    tau = ops._tau(threshold)
+    n, d = rows.shape
+    for name, v in (("chunk", chunk), ("max_pairs", max_pairs)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+            raise ValueError("%s must be None or an integer >= 1, got %r" % (name, v))
+    parts, total = [], 0
+    if index is None:
+        if chunk is None:                                     # ~256 MB of fp32 scores per block
+            chunk = max(ops.JOIN_BLOCK, (1 << 28) // (4 * n) // ops.JOIN_BLOCK * ops.JOIN_BLOCK)
+        fp32 = None if d % 4 == 0 else ops.DescriptorIndex(rows, "ND")
+        try:
+            for lo in range(0, n, chunk):
+                hi = min(n, lo + chunk)
+                if fp32 is None:                              # the upper triangle only: columns lo .. n-1, read in place
+                    sc = ops.scores_rowmajor(rows[lo:], rows[lo:hi], "ND")
+                    off, ids, vals = ops.range_select(sc, tau, diag=0)
+                    parts.append((off, ids + lo, vals))
+                else:
+                    sc = fp32.scores(rows[lo:hi], "ND")
+                    parts.append(ops.range_select(sc, tau, diag=lo))
+                del sc
+                total += parts[-1][1].numel()
+                if max_pairs is not None and total > max_pairs:
+                    raise ValueError("self_join: more than max_pairs=%d pairs at threshold %r" % (max_pairs, threshold))
+        finally:
+            if fp32 is not None:
+                fp32.close()
+        return _concat(parts, rows.device)
+    # the join kernel runs groups of 16 row blocks against every later block: 2048 rows of A is one group; 32 768 rows per chunk
+    # keep the candidate buffer small at the thresholds this targets and the per-chunk synchronisation rare
+    chunk = 1 << 15 if chunk is None else -(-chunk // ops.JOIN_BLOCK) * ops.JOIN_BLOCK
+    stats = _join_stats(index, rows)
+    capacity = 1 << 20
+    for lo in range(0, n, chunk):
+        hi = min(n, lo + chunk)
+        pairs = _candidates(index, stats, index, stats, tau, lo, hi, True, capacity, "use a smaller chunk")
+        capacity = max(capacity, pairs.numel())
+        parts.append(ops.join_resolve(rows, rows, pairs, tau, lo, hi - lo))
+        del pairs
+        total += parts[-1][1].numel()
+        if max_pairs is not None and total > max_pairs:
+            raise ValueError("self_join: more than max_pairs=%d pairs at threshold %r" % (max_pairs, threshold))
+    return _concat(parts, rows.device)
