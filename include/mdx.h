@@ -25,6 +25,20 @@
  *    the last failure on the calling thread is mdx_last_error().  Nothing aborts.
  *  - One host thread per device at a time; handles are not internally locked.
  *  - Matrices are dense fp32.  "row-major [a,b]" means element (i,j) at i*b+j.
+ *
+ * Alignment
+ *    Every device pointer must be aligned to the size of ITS ELEMENT (4 bytes for float / int32, 8 for int64 / double, 2
+ *    for int16, 1 for uint8 / int8) and to nothing more -- a row slice of a larger tensor is a legal argument and gives
+ *    the same bits as an aligned copy (where a kernel has a 16-byte path it picks it by the address, or issues its 16-byte
+ *    accesses at element alignment) -- except:
+ *      pointer                                                     alignment   otherwise
+ *      `workspace` of every entry point that takes one             16 bytes    MDX_ERR_INVALID
+ *      `memory` of mdx_index_create_in                             256 bytes   MDX_ERR_WORKSPACE
+ *      `stats` of mdx_join_stats, `stats_a` / `stats_b` of
+ *        mdx_join_candidates (one {p, q, r, w} per 16-byte word)   16 bytes    MDX_ERR_INVALID
+ *      `planes` of mdx_jpeg_pixels (rows of 8 samples as 2 words)  4 bytes     MDX_ERR_INVALID
+ *    No entry point reads or writes outside the extents stated for its arguments, reads a workspace or an output before
+ *    writing it, or writes an input that is not documented as updated in place (tests/test_gpu_memcontract.py).
  */
 #ifndef MDX_H
 #define MDX_H

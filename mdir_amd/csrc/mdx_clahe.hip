@@ -287,6 +287,7 @@ int mdx_clahe_u8_to_chw(const uint8_t *rgb, int64_t B, int64_t H, int64_t W, int
         set_error("mdx_clahe_u8_to_chw: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_clahe_u8_to_chw");
     hipStream_t s = (hipStream_t)stream;
     uint8_t *l8 = (uint8_t *)workspace, *luts = l8 + round_up(B * H * W, 256);
     uint8_t *l8_out = luts + round_up(B * (int64_t)tiles_x * tiles_y * 256, 256);

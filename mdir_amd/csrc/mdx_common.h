@@ -28,6 +28,10 @@ int probe_lds_order(hipStream_t s);
         }                                         \
     } while (0)
 
+// every workspace of the ABI: 16-byte aligned (include/mdx.h, "Alignment"); the carved pieces hold 8- and 16-byte words
+#define MDX_CHECK_WORKSPACE_ALIGNED(ws, who) \
+    MDX_CHECK_ARG((((uintptr_t)(ws)) & 15) == 0, "%s: workspace must be 16-byte aligned", who)
+
 #define MDX_HIP(call)                                                                   \
     do {                                                                                \
         hipError_t e_ = (call);                                                         \

@@ -696,6 +696,7 @@ int mdx_knn_graph(const int64_t *ids, const float *sims, int64_t n, int64_t k, f
         set_error("mdx_knn_graph: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_graph");
     hipStream_t s = (hipStream_t)stream;
     float *rinv = (float *)workspace;
     hipLaunchKernelGGL(knn_graph_edges_kernel, dim3((unsigned)ceil_div(n, DIF_WAVES)), dim3(64 * DIF_WAVES), 0, s, ids, sims,
@@ -798,6 +799,7 @@ int mdx_knn_graph_weights(const int64_t *ids, const float *sims, int64_t n, int6
         set_error("mdx_knn_graph_weights: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_graph_weights");
     hipLaunchKernelGGL(knn_graph_edges_kernel, dim3((unsigned)ceil_div(n, DIF_WAVES)), dim3(64 * DIF_WAVES), 0,
                        (hipStream_t)stream, ids, sims, n, k, gamma, cols, w, counts, (float *)workspace);
     MDX_LAUNCH_CHECK();

@@ -473,6 +473,7 @@ int mdx_gram_f64(const double *a, int64_t d, int64_t n, const double *center, do
         set_error("mdx_gram_f64: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_gram_f64");
     hipStream_t s = (hipStream_t)stream;
     const int64_t ld = padded_ld(d);
     double *at = (double *)workspace, *part = (double *)((char *)workspace + transposed_bytes(n, d));
@@ -535,6 +536,7 @@ int mdx_project_f64(const double *p, int64_t dout, int64_t d, const double *x, i
         set_error("mdx_project_f64: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_project_f64");
     MDX_CHECK_ARG(ceil_div(dout, (int64_t)64) < 65536, "mdx_project_f64: too many tiles");
     hipStream_t s = (hipStream_t)stream;
     double *pt = (double *)workspace;

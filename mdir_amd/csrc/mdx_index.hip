@@ -775,6 +775,7 @@ static int scores_impl(const mdx_index *ix, const float *queries, int64_t nq, in
                   (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores");
     hipStream_t s = (hipStream_t)stream;
     f32x4 *qtiles = (f32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS);
@@ -866,6 +867,7 @@ int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *quer
         set_error("mdx_scores_rowmajor: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores_rowmajor");
     hipStream_t s = (hipStream_t)stream;
     f32x4 *qtiles = (f32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS), KB = round_up(d, 64) / TILE_K, RT = ceil_div(n, TILE_ROWS);
@@ -910,6 +912,7 @@ int mdx_scores_ex(const mdx_index *ix, const float *queries, int64_t nq, int qla
         set_error("mdx_scores_ex: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores_ex");
     hipStream_t s = (hipStream_t)stream;
     u32x4 *qp = (u32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS), NC = ix->KB / 2;

@@ -511,6 +511,7 @@ int mdx_center_rows(const float *src, int64_t n, int64_t d, int layout, const fl
 int mdx_join_stats(const mdx_index *index, const float *rows, int64_t ld, float *stats, void *stream)
 {
     MDX_CHECK_ARG(index && rows && stats, "mdx_join_stats: NULL pointer");
+    MDX_CHECK_ARG(((uintptr_t)stats & 15) == 0, "mdx_join_stats: stats must be 16-byte aligned (one {p, q, r, w} per 16-byte word)");
     const void *tiles = nullptr;
     const float *scales = nullptr;
     int64_t n = 0, RT = 0, KB = 0, d = 0;
@@ -528,6 +529,7 @@ int mdx_join_candidates(const mdx_index *a, const float *stats_a, const mdx_inde
                         int symmetric, float tau, uint64_t *pairs, int64_t capacity, int64_t *count, void *stream)
 {
     MDX_CHECK_ARG(a && stats_a && b && stats_b && pairs && count, "mdx_join_candidates: NULL pointer");
+    MDX_CHECK_ARG((((uintptr_t)stats_a | (uintptr_t)stats_b) & 15) == 0, "mdx_join_candidates: stats_a / stats_b must be 16-byte aligned");
     MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_join_candidates: tau must be finite");
     MDX_CHECK_ARG(capacity >= 0, "mdx_join_candidates: capacity=%lld < 0", (long long)capacity);
     MDX_CHECK_ARG(!symmetric || a == b, "mdx_join_candidates: the self-join needs a == b");
@@ -594,6 +596,7 @@ int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int6
         set_error("mdx_join_resolve: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_join_resolve");
     Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};     // the + 256 of the size covers the alignment
     uint64_t *cs, *key, *key2;
     int32_t *idx, *idx2;
@@ -644,6 +647,7 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
         set_error("mdx_range_select: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_range_select");
     Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};
     int64_t *counts, *hid;
     uint64_t *key, *key2;

@@ -794,6 +794,7 @@ int mdx_jpeg_coefficients(const uint8_t *file, int64_t size, int16_t *coef, int6
 int mdx_jpeg_pixels(const int16_t *coef, const uint16_t *quant, const mdx_jpeg_info *info, uint8_t *planes, uint8_t *rgb, void *stream)
 {
     MDX_CHECK_ARG(coef && quant && info && planes && rgb, "mdx_jpeg_pixels: NULL pointer");
+    MDX_CHECK_ARG(((uintptr_t)planes & 3) == 0, "mdx_jpeg_pixels: planes must be 4-byte aligned (rows of 8 samples are stored as two words)");
     MDX_CHECK_ARG(info->supported && info->nblocks > 0 && info->width > 0 && info->height > 0, "mdx_jpeg_pixels: unsupported image");
     MDX_CHECK_ARG(info_consistent(*info), "mdx_jpeg_pixels: the geometry is not one mdx_jpeg_probe reports (sampling factors, block counts and "
                                           "offsets must follow from width, height and the component count)");

@@ -31,6 +31,22 @@ __device__ __forceinline__ float pool_elem(float x, float p, float eps)
     return x;
 }
 
+// a lane's part of a plane read in 16-byte pieces: the order of the sum is the same for both vector types
+template <int KIND, int MODE, typename V4>
+__device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int HW, float p, float eps, int lane, float acc)
+{
+    const V4 *s4 = (const V4 *)src;
+    const int n4 = HW >> 2;
+    for (int i = lane; i < n4; i += 64) {
+        const V4 v = s4[i];
+        const float a = pool_elem<KIND, MODE>(v.x, p, eps), b = pool_elem<KIND, MODE>(v.y, p, eps);
+        const float c = pool_elem<KIND, MODE>(v.z, p, eps), d = pool_elem<KIND, MODE>(v.w, p, eps);
+        if (KIND == MDX_POOL_MAC) acc = fmaxf(acc, fmaxf(fmaxf(a, b), fmaxf(c, d)));
+        else acc += (a + b) + (c + d);
+    }
+    return acc;
+}
+
 // one wave reduces one (image, channel) plane; every lane returns the pooled value
 template <int KIND, int MODE>
 __device__ __forceinline__ float pool_plane(const float *__restrict__ src, bool wide, int HW, float p, float inv_p, float eps,
@@ -38,15 +54,12 @@ __device__ __forceinline__ float pool_plane(const float *__restrict__ src, bool 
 {
     float acc = KIND == MDX_POOL_MAC ? -INFINITY : 0.0f;
     if (wide) {
-        const float4 *s4 = (const float4 *)src;
-        const int n4 = HW >> 2;
-        for (int i = lane; i < n4; i += 64) {
-            const float4 v = s4[i];
-            const float a = pool_elem<KIND, MODE>(v.x, p, eps), b = pool_elem<KIND, MODE>(v.y, p, eps);
-            const float c = pool_elem<KIND, MODE>(v.z, p, eps), d = pool_elem<KIND, MODE>(v.w, p, eps);
-            if (KIND == MDX_POOL_MAC) acc = fmaxf(acc, fmaxf(fmaxf(a, b), fmaxf(c, d)));
-            else acc += (a + b) + (c + d);
-        }
+        // H*W % 4 == 0.  The plane of a sliced feature map starts at any multiple of 4 bytes; the summation order (hence
+        // every bit of the result) must not depend on where the caller's tensor lies, so a plane off the 16-byte grid is
+        // read in the same pieces through 16-byte loads at dword alignment
+        typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+        if (((uintptr_t)src & 15) == 0) acc = pool_pieces<KIND, MODE, float4>(src, HW, p, eps, lane, acc);
+        else acc = pool_pieces<KIND, MODE, f32x4u>(src, HW, p, eps, lane, acc);
     } else {
         for (int i = lane; i < HW; i += 64) {
             const float a = pool_elem<KIND, MODE>(src[i], p, eps);
@@ -69,7 +82,7 @@ __global__ __launch_bounds__(256) void pool_kernel(const float *__restrict__ fea
     const int lane = threadIdx.x & 63;
     const int64_t plane = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (plane >= planes) return;
-    const bool wide = (HW & 3) == 0 && ((uintptr_t)feat & 15) == 0;
+    const bool wide = (HW & 3) == 0;
     const float r = pool_plane<KIND, MODE>(feat + plane * HW, wide, HW, p, inv_p, eps, lane);
     if (lane == 0) out[plane] = r;
 }
@@ -93,7 +106,7 @@ __global__ __launch_bounds__(256) void pool_multi_kernel(PoolMaps maps, int S, f
     while (s + 1 < S && plane >= maps.first[s + 1]) ++s;
     const float *feat = maps.feat[s];
     const int HW = maps.hw[s];
-    const bool wide = (HW & 3) == 0 && ((uintptr_t)feat & 15) == 0;
+    const bool wide = (HW & 3) == 0;
     const float r = pool_plane<KIND, MODE>(feat + (plane - maps.first[s]) * HW, wide, HW, p, inv_p, eps, lane);
     if (lane == 0) out[plane] = r;
 }
@@ -443,6 +456,7 @@ int mdx_rmac(const float *feat, int B, int C, int H, int W, const int32_t *regio
         set_error("mdx_rmac: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_rmac");
     RmacGrid grid;
     int rc = fill_grid(&grid, regions, nregions, H, W, "mdx_rmac");
     if (rc != MDX_OK) return rc;

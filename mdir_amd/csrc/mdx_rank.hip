@@ -994,6 +994,7 @@ static int rank_impl(const float *scores, int64_t n, int64_t nq, int64_t id_offs
                   (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, who);
     RankWs ws;
     carve(&ws, (char *)workspace, n, nq);
     // MDX_SORT_NO_PACK=1: the (key word, id word) layout also for small n (tests run both)
@@ -1718,6 +1719,7 @@ int mdx_topk(const float *scores, int64_t n, int64_t nq, int64_t k, int64_t id_o
         set_error("mdx_topk: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_topk");
     // k <<< n (serving): sampled threshold, one pass over the scores
     if (n >= 16384 && k <= 1024 && 256 * k <= n && sampled_workspace(n, nq) <= workspace_bytes && !getenv("MDX_NO_SAMPLED_TOPK"))
         return topk_sampled(scores, n, nq, k, id_offset, top_ids, top_scores, workspace, (hipStream_t)stream);

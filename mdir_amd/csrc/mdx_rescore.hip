@@ -358,6 +358,7 @@ int mdx_rescore(const float *rows, int64_t n, int64_t d, int64_t ld, const float
         set_error("mdx_rescore: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
         return MDX_ERR_WORKSPACE;
     }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_rescore");
     hipStream_t s = (hipStream_t)stream;
     float *sc = (float *)workspace;
     const bool vec = ld % 4 == 0 && ((uintptr_t)rows & 15) == 0;       // 16-byte pieces at 16-byte addresses
