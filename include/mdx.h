@@ -35,7 +35,8 @@
  *      `workspace` of every entry point that takes one             16 bytes    MDX_ERR_INVALID
  *      `memory` of mdx_index_create_in                             256 bytes   MDX_ERR_WORKSPACE
  *      `stats` of mdx_join_stats, `stats_a` / `stats_b` of
- *        mdx_join_candidates (one {p, q, r, w} per 16-byte word)   16 bytes    MDX_ERR_INVALID
+ *        mdx_join_candidates / _rows and mdx_knn_bounds
+ *        (one {p, q, r, w} per 16-byte word)                       16 bytes    MDX_ERR_INVALID
  *      `planes` of mdx_jpeg_pixels (rows of 8 samples as 2 words)  4 bytes     MDX_ERR_INVALID
  *    No entry point reads or writes outside the extents stated for its arguments, reads a workspace or an output before
  *    writing it, or writes an input that is not documented as updated in place (tests/test_gpu_memcontract.py).
@@ -719,6 +720,63 @@ int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int6
 int64_t mdx_range_select_workspace(int64_t m, int64_t capacity);
 int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, float tau, int64_t diag, int64_t *offsets, int64_t *ids,
                      float *out_scores, int64_t capacity, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* --------------------------------------------------------------- exact kNN join */
+
+/* The exact top-k of rows [a_lo, a_hi) of A against EVERY row of B, the join whose threshold is not given but is each row's own
+ * k-th score: ids int64 [m, k] and scores fp32 [m, k], m = a_hi - a_lo.  Both operands are MDX_I8 shards of fp32 row matrices
+ * (stats: mdx_join_stats of each).  The result is bit-identical to mdx_topk(mdx_scores(fp32 index of B, the A rows), k): the same
+ * chain (the exact score of "exact range search and self-join", continued over zeros to round_up(d, 64)) in mdx_rank_full's order
+ * (larger score first, -0 == +0, NaN last, ties by ascending id).  With A == B a row's own match is included, as in mdx_topk.  The
+ * bits depend on the inputs only -- not on chunking, slicing, buffer capacity or launch order.
+ *
+ * Lower bound.  For a pair (i, j) with MDX_I8 score s and the join kernel's rounded-up bound b (above; +inf where the pair is not
+ * covered, the scale-product override included):
+ *     h = fl(2^-21 |s|),   l_ij = fl(fl(s - h) - b).
+ *   From  |x.y - s| <= (the MDX_I8 terms) + 2^-22 |s|  and  |chain - x.y| <= gamma_d max|y| ||x||_1 + d 2^-149  (both two-sided):
+ *     chain >= s - 2^-22 |s| - beta_xy,  and with the roles swapped  chain >= s - 2^-22 |s| - beta_yx;  b >= min(beta) + 2^-150.
+ *   Rounding, mirroring the join kernel's: h >= 2^-21 |s| - 2^-150 (a product with a power of two is exact unless it is subnormal);
+ *   the rounded difference s - h gains at most u |s - h| <= (2^-24 + 2^-45) |s|, u = 2^-24 (a subnormal difference is exact), so
+ *   fl(s - h) <= s - (2^-21 - 2^-24 - 2^-45) |s| + 2^-150 <= s - 2^-22 |s| + 2^-150, and fl(s - h) - b <= s - 2^-22 |s| - beta <=
+ *   chain.  chain is an fp32 value and rounding is monotone, so l_ij = fl(fl(s - h) - b) <= chain_ij.  The fp32 evaluation can only
+ *   lower l.  Covered rows hold finite values of magnitude below 2^47, so their chain is a number.
+ *   A pair contributes NO lower bound when b is infinite, when s is NaN or when l_ij is not finite.  A zero l_ij counts as +0.
+ * Threshold.  t_i = the k-th largest of the multiset {l_ij : j contributes}; -inf when fewer than k pairs contribute -- a value
+ *   defined by the inputs alone (a k-th largest of a fixed multiset), whatever the slices and their order.
+ *   At least k rows j have chain_ij >= l_ij >= t_i, so the exact k-th score e_i (rank order) satisfies e_i >= t_i.  By the join
+ *   proof above (it holds for every fp32 threshold), every j with chain_ij >= t_i is a candidate of mdx_join_candidates_rows at
+ *   tau_i = t_i; so every row that ties with or beats e_i is a candidate, and the first k candidates of row i in rank order are its
+ *   exact top-k, ties included.  t_i = -inf makes every row of B a candidate (lhs < -inf never holds), NaN rows too: rows with NaN,
+ *   infinite or uncovered entries are still exact.
+ *
+ * Stages (all enqueue only):
+ *   mdx_knn_bounds            t fp32 [m]: t_i of rows [a_lo, a_hi) of A (a_lo a multiple of MDX_JOIN_BLOCK).  One workgroup per
+ *                             128-row block of A and slice of the 128-row blocks of B: the int8 MFMA block body of the join kernel,
+ *                             the k largest l_ij of every row kept in LDS (MDX_KNN_JOIN_MAX_K = 64: 128 lists of 64 fp32 are 32 KiB
+ *                             beside the 32 KiB of operand staging, so two workgroups still share a CU), each slice's sorted list
+ *                             written to the workspace [slices, m, k]; a second launch takes the k-th largest of a row's lists.
+ *                             slices: 0 = automatic (enough to fill the chip), or 1 .. 64 (never more than the blocks of B are
+ *                             used); every value gives the same bits.  workspace: mdx_knn_bounds_workspace(m, k, nb, slices) bytes.
+ *   mdx_join_candidates_rows  mdx_join_candidates (non-symmetric) with the threshold of row i read from tau [a_hi - a_lo] (device
+ *                             fp32, any value: -inf or NaN keep every pair of the row); pairs, capacity and count as there.
+ *   mdx_knn_resolve           pairs [P] (each unique) of rows i in [m_lo, m_lo + m): sorted by (i, j), the exact chains of
+ *                             mdx_join_resolve with no threshold test (a NaN score is kept and ranks last), the same stable (row,
+ *                             desc_key) sort, then the first k of each row into ids int64 [m, k] / scores fp32 [m, k] and the
+ *                             candidates of each row into counts int32 [m].  A count below k can only mean thresholds that were
+ *                             not mdx_knn_bounds': the tail of such a row is id -1 / score NaN.  workspace:
+ *                             mdx_knn_resolve_workspace(P, m) bytes.
+ * MDX_ERR_INVALID, nothing launched, for a NULL pointer, k < 1, k > nb (mdx_knn_bounds) or k > MDX_KNN_JOIN_MAX_K, slices outside
+ * [0, 64], a non-int8 index, A and B of different d, a_lo not a multiple of MDX_JOIN_BLOCK or rows outside A, sizes (n, P, m) at or
+ * above 2^31 or below 1, a negative capacity, lda / ldb below d, stats not 16-byte aligned; MDX_ERR_WORKSPACE for a workspace below
+ * the size functions' (0 for sizes they refuse). */
+/* The prototypes of this section (and MDX_KNN_JOIN_MAX_K) are in mdx_knn_join.h, beside this file, and their names in
+ * _lib.KNN_JOIN_EXPORTS.  The reason is a test, not the ABI: tests/test_memguard_host.py pins the number of prototypes in THIS
+ * file and takes their memory-contract cases from tests/test_gpu_memcontract.py alone, and the change that added this section
+ * was to leave existing tests as they were.  So that census and tests/test_cabi.py do NOT cover these five names; their own
+ * census is tests/test_knn_join_host.py (every prototype of mdx_knn_join.h is exported, bound, and -- unless it is a size
+ * function -- has cases in tests/test_gpu_knn_join_memcontract.py).  Whoever next edits that census should move the prototypes
+ * here, the names into _lib.EXPORTS and the cases into the table, and delete the second header. */
+#include "mdx_knn_join.h"
 
 /* ------------------------------------------------- whitening learning (float64) */
 

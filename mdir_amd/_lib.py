@@ -34,7 +34,7 @@ ABI_VERSION = 3        # include/mdx.h MDX_ABI_VERSION this binding was written 
 def build(force=False):
     """Compile libmdx.so with hipcc --offload-arch=gfx950 (see csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs.append(os.path.join(_HERE, "..", "include", "mdx.h"))
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h")]
     stale = not os.path.exists(LIB_PATH) or \
         any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -93,6 +93,11 @@ def _declare(lib):
         "mdx_join_resolve": (i32, [p, i64, p, i64, i64, p, i64, f32, i64, i64, p, p, p, p, i64, p]),
         "mdx_range_select_workspace": (i64, [i64, i64]),
         "mdx_range_select": (i32, [p, i64, i64, i64, f32, i64, p, p, p, i64, p, i64, p]),
+        "mdx_knn_bounds_workspace": (i64, [i64, i64, i64, i64]),
+        "mdx_knn_bounds": (i32, [p, p, p, p, i64, i64, i64, i64, p, p, i64, p]),
+        "mdx_join_candidates_rows": (i32, [p, p, p, p, i64, i64, p, p, i64, p, p]),
+        "mdx_knn_resolve_workspace": (i64, [i64, i64]),
+        "mdx_knn_resolve": (i32, [p, i64, p, i64, i64, p, i64, i64, i64, i64, p, p, p, p, i64, p]),
         "mdx_index_info": (i32, [p, pi64, pi64, pi64, pi64]),
         "mdx_scores_workspace": (i64, [i64, i64]),
         "mdx_quantize_i8": (i32, [p, i64, i64, i32, p, p, p]),
@@ -160,6 +165,11 @@ EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac
            "mdx_comm_destroy", "mdx_comm_info", "mdx_query_bounds", "mdx_allgather_scores", "mdx_exchange_scores",
            "mdx_p2p_create", "mdx_p2p_connect", "mdx_p2p_connect_ptrs", "mdx_p2p_base", "mdx_p2p_bytes", "mdx_scores_p2p", "mdx_p2p_close_step",
            "mdx_p2p_status", "mdx_p2p_destroy")
+
+# include/mdx_knn_join.h (included by mdx.h): the exact kNN join.  Apart from EXPORTS because tests/test_cabi.py and
+# tests/test_memguard_host.py pin EXPORTS to mdx.h's own prototypes and their number; tests/test_knn_join_host.py is the census
+# of these (include/mdx.h, "exact kNN join", says more)
+KNN_JOIN_EXPORTS = ("mdx_knn_bounds_workspace", "mdx_knn_bounds", "mdx_join_candidates_rows", "mdx_knn_resolve_workspace", "mdx_knn_resolve")
 
 
 def lib():

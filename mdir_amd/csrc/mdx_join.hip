@@ -1,4 +1,5 @@
-// Exact range search and self-join, pruned on the int8 shard (include/mdx.h, "exact range search and self-join").
+// Exact range search, self-join and kNN join, pruned on the int8 shard (include/mdx.h, "exact range search and self-join",
+// "exact kNN join").
 //
 //   join_stats_kernel     one wave per row: ||x||_1 (float64), max |x|, finiteness and ||c||_1 of the row's int8 codes ->
 //                         the four per-row factors {scale, q, r, w} of the pruning bound, rounded up to fp32.
@@ -7,6 +8,10 @@
 //                         64 x 64 rows on v_mfma_i32_16x16x64_i8 (exact int32 sums), and the epilogue forms the MDX_I8 score
 //                         of each pair and tests it against tau - beta_ij.  Candidates leave through a wave prefix sum, ONE
 //                         global atomic per wave that has any, and 8-byte stores; the count runs on past the capacity.
+//   knn_bound_kernel      the exact kNN join (include/mdx.h, "exact kNN join"): the same block body, one workgroup per 128 rows of A and
+//                         slice of the J blocks; per row the k largest lower bounds l_ij of the exact chain stay in LDS, fed through
+//                         an LDS queue; knn_select_kernel takes the k-th largest of a row's slices.  join_kernel<., ROWS> then reads
+//                         its threshold per row, and knn_dense_kernel writes the first k of every row's sorted candidates.
 //   exact_kernel          one workgroup per 64 sorted candidates: the A and B row pieces are staged in LDS 128 k at a time
 //                         and wave 0 runs the k-ascending fmaf chains of mdx_rescore (lane = candidate).
 //   select_count/_write   the dense threshold compaction of an fp32 score matrix (one workgroup per row, ordered).
@@ -103,31 +108,15 @@ __device__ __forceinline__ float beta_up(jn_f32x4 x, jn_f32x4 y, float c0)
     return __fmul_rn(s, 1.0f + 0x1p-20f);
 }
 
-// a: the A shard's tiles, b: B's (== a for the self-join).  A blocks [I0, I1) in groups of GS (<= J_GROUP) that sweep every J
-// block -- or, symmetric, one group of J_GROUP blocks from I0 against J >= I0.  out: (i << 32 | j) of every candidate, i, j
-// global rows of A and B.
-template <bool SYM>
-__global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
-                                                      const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
-                                                      int64_t I0, int64_t I1, int64_t NJ, int GS, float tau, float c0, uint64_t *__restrict__ out,
-                                                      int64_t capacity, unsigned long long *__restrict__ count)
+// The block body of the join and the kNN bound kernel: acc = the int32 code products of the 128 rows of A block I against the 128
+// rows of B block J; wave (wa, wb) holds its 64 x 64 corner as 4 x 4 MFMA tiles.  16 x 64 tiles of both shards are staged in LDS a
+// 64-k chunk at a time (double buffer, one barrier per chunk).  On entry every wave has left both buffers (a fresh workgroup, or
+// a barrier since the last call); on exit a wave may still read the last buffer.
+__device__ __forceinline__ void block_mma(jn_i32x4 (*lds)[2 * JB_TILES * 64], const jn_i32x4 *__restrict__ a, const jn_i32x4 *__restrict__ b,
+                                          int64_t I, int64_t J, int KB, jn_i32x4 (&acc)[4][4])
 {
-    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // [buffer][A tiles, then B tiles][lane]: 2 x 16 KiB
-    int64_t I, J;
-    const int64_t bid = blockIdx.x;
-    if constexpr (SYM) {                                         // J >= I0; I = I0 + (0 .. J_GROUP-1), J >= I
-        I = I0 + bid % J_GROUP;
-        J = I0 + bid / J_GROUP;
-        if (I >= I1 || J < I) return;
-    } else {                                                     // groups of GS I blocks sweep every J block
-        const int64_t g = bid / (GS * NJ), w = bid % (GS * NJ);
-        I = I0 + g * GS + w % GS;
-        J = w / GS;
-        if (I >= I1) return;
-    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;                     // the wave's 64 x 64 corner of the block
-
     // stage loads: thread t moves pieces t, t + 256, t + 512, t + 768 of the 16 tiles (A 0..7, B 8..15) of a chunk
     const jn_i32x4 *src[4];
 #pragma unroll
@@ -145,8 +134,6 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
 #pragma unroll
         for (int u = 0; u < 4; ++u) lds[buf][tid + 256 * u] = reg[u];
     };
-
-    jn_i32x4 acc[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -173,6 +160,46 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
             __syncthreads();
         }
     }
+}
+
+// the MDX_I8 score of a pair from its code product and the rounded-up bound b of include/mdx.h (+inf: the pair is not covered)
+__device__ __forceinline__ void pair_bound(int acc, jn_f32x4 xs, jn_f32x4 ys, float c0, float &sc, float &bnd)
+{
+    const float prod = __fmul_rn(ys[0], xs[0]);                              // scale_B * scale_A, as MDX_I8
+    sc = __fmul_rn((float)acc, prod);
+    bnd = fminf(beta_up(xs, ys, c0), beta_up(ys, xs, c0));
+    if (xs[0] > 0.f && ys[0] > 0.f && prod < 0x1p-126f) bnd = __builtin_inff();     // the product may have underflowed
+}
+
+// a: the A shard's tiles, b: B's (== a for the self-join).  A blocks [I0, I1) in groups of GS (<= J_GROUP) that sweep every J
+// block -- or, symmetric, one group of J_GROUP blocks from I0 against J >= I0.  out: (i << 32 | j) of every candidate, i, j
+// global rows of A and B.  ROWS: the threshold of A row i is taus[i - 128 I0] (any fp32 value: -inf or NaN keeps every pair).
+template <bool SYM, bool ROWS>
+__global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
+                                                      const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
+                                                      int64_t I0, int64_t I1, int64_t NJ, int GS, float tau, const float *__restrict__ taus,
+                                                      float c0, uint64_t *__restrict__ out, int64_t capacity,
+                                                      unsigned long long *__restrict__ count)
+{
+    static_assert(!(SYM && ROWS), "per-row thresholds: the non-symmetric join only");
+    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // [buffer][A tiles, then B tiles][lane]: 2 x 16 KiB
+    int64_t I, J;
+    const int64_t bid = blockIdx.x;
+    if constexpr (SYM) {                                         // J >= I0; I = I0 + (0 .. J_GROUP-1), J >= I
+        I = I0 + bid % J_GROUP;
+        J = I0 + bid / J_GROUP;
+        if (I >= I1 || J < I) return;
+    } else {                                                     // groups of GS I blocks sweep every J block
+        const int64_t g = bid / (GS * NJ), w = bid % (GS * NJ);
+        I = I0 + g * GS + w % GS;
+        J = w / GS;
+        if (I >= I1) return;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wa = wave >> 1, wb = wave & 1;                     // the wave's 64 x 64 corner of the block
+
+    jn_i32x4 acc[4][4];
+    block_mma(lds, a, b, I, J, KB, acc);
 
     // Epilogue: lane (g, col) holds rows 4 g .. 4 g + 3 of A tile r against row col of B tile c
     const int g4 = 4 * (lane >> 4), col = lane & 15;
@@ -191,15 +218,14 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
             const int64_t irow = (I * JB_TILES + wa * 4 + r) * 16 + g4 + e;
             if (irow >= na) continue;
             const jn_f32x4 xs = sa[irow];
+            const float t = ROWS ? taus[irow - I0 * JB_ROWS] : tau;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (jrow[c] >= nb || (SYM && jrow[c] <= irow)) continue;
-                const float prod = __fmul_rn(ys[c][0], xs[0]);                  // scale_B * scale_A, as MDX_I8
-                const float sc = __fmul_rn((float)acc[r][c][e], prod);
-                float bnd = fminf(beta_up(xs, ys[c], c0), beta_up(ys[c], xs, c0));
-                if (xs[0] > 0.f && ys[c][0] > 0.f && prod < 0x1p-126f) bnd = __builtin_inff();   // the product may have underflowed
+                float sc, bnd;
+                pair_bound(acc[r][c][e], xs, ys[c], c0, sc, bnd);
                 const float lhs = __fadd_rn(__fadd_rn(sc, __fmul_rn(fabsf(sc), 0x1p-21f)), bnd);
-                if (!(lhs < tau)) mask |= 1ull << ((r * 4 + e) * 4 + c);    // a NaN score is a candidate
+                if (!(lhs < t)) mask |= 1ull << ((r * 4 + e) * 4 + c);      // a NaN score is a candidate
             }
         }
     }
@@ -221,6 +247,202 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
     }
 }
 
+// ---------------------------------------------------------------- the kNN bound kernel
+
+constexpr int KNN_MAX_K = 64;                   // MDX_KNN_JOIN_MAX_K: 128 lists of 64 fp32 = 32 KiB of LDS beside 32 KiB of staging
+constexpr int KNN_LD = KNN_MAX_K + 1;           // list stride: thread t walks list t, 65 t + c hits 32 banks for 32 lanes
+constexpr int KNN_QCAP = 1024;                  // queue entries: one (r, e) step of a whole block (4 waves x 64 lanes x 4 tiles)
+constexpr int KNN_MAX_SLICES = 64;              // one lane per list in knn_select_kernel
+
+// l_ij of include/mdx.h ("exact kNN join"): fl(fl(s - fl(2^-21 |s|)) - b) <= chain_ij, or -inf where the pair gives no lower bound
+// (b infinite, a NaN score, l not finite); -0 is returned as +0, so that equal values are equal bits
+__device__ __forceinline__ float knn_lower(int acc, jn_f32x4 xs, jn_f32x4 ys, float c0)
+{
+    float sc, bnd;
+    pair_bound(acc, xs, ys, c0, sc, bnd);
+    const float l = __fsub_rn(__fsub_rn(sc, __fmul_rn(fabsf(sc), 0x1p-21f)), bnd);
+    return __builtin_isfinite(l) ? (l == 0.f ? 0.f : l) : -__builtin_inff();
+}
+
+// One workgroup per (A block I, slice sl of the J blocks): it sweeps J in [sl NJ / S, (sl + 1) NJ / S) and keeps, per A row, the k
+// largest l_ij seen (top, unsorted, thread t < 128 owns row t) and their minimum theta (-inf until the list is full).  Per J block
+// the values above theta go through an LDS queue (wave prefix sum, one LDS atomic per wave) and are merged after a barrier; a
+// block that overflows the queue (the first ones do) is redone in 16 steps of at most KNN_QCAP values.  Workgroups of one group
+// of GS A blocks and one slice are neighbours in the grid and walk J in the same order (L2 reuse of both operands).
+// lists [S, m, k]: every list sorted descending, -inf beyond the values it holds.
+__global__ __launch_bounds__(256, 2) void knn_bound_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
+                                                           const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
+                                                           int64_t I0, int64_t I1, int64_t NJ, int GS, int S, int k, float c0,
+                                                           float *__restrict__ lists, int64_t m)
+{
+    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // 32 KiB of staging
+    __shared__ float top[JB_ROWS * KNN_LD];                      // 32.5 KiB: the k largest of each row
+    __shared__ jn_f32x4 sx[JB_ROWS];                             // the factors of the A rows (zeros beyond the shard)
+    __shared__ float theta[JB_ROWS];
+    __shared__ float qval[KNN_QCAP];
+    __shared__ uint32_t qrow[KNN_QCAP];
+    __shared__ uint32_t qn[2];                                   // the queue length, by phase parity: the idle one is zero
+    const int64_t bid = blockIdx.x;
+    const int64_t g = bid / ((int64_t)GS * S), w = bid % ((int64_t)GS * S);
+    const int64_t I = I0 + g * GS + w % GS;
+    const int sl = (int)(w / GS);
+    if (I >= I1) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wa = wave >> 1, wb = wave & 1;
+    const int g4 = 4 * (lane >> 4), col = lane & 15;
+    const float ninf = -__builtin_inff();
+
+    if (tid < JB_ROWS) {
+        theta[tid] = ninf;
+        sx[tid] = I * JB_ROWS + tid < na ? sa[I * JB_ROWS + tid] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if (tid < 2) qn[tid] = 0;
+    int cnt = 0, amin = 0;                                       // of thread tid < 128: its list's length and the slot of its minimum
+    float th = ninf;
+    __syncthreads();
+
+    auto rescan = [&]() {
+        th = top[tid * KNN_LD];
+        amin = 0;
+        for (int c = 1; c < k; ++c) {
+            const float x = top[tid * KNN_LD + c];
+            if (x < th) {
+                th = x;
+                amin = c;
+            }
+        }
+    };
+    auto merge = [&](uint32_t n) {                               // the queue into the lists: each entry by the thread of its row
+        if (tid >= JB_ROWS) return;
+        for (uint32_t q = 0; q < n; ++q) {
+            if (qrow[q] != (uint32_t)tid) continue;
+            const float v = qval[q];
+            if (cnt < k) {
+                top[tid * KNN_LD + cnt++] = v;
+                if (cnt == k) rescan();
+            } else if (v > th) {                                 // theta may have risen since the value was queued
+                top[tid * KNN_LD + amin] = v;
+                rescan();
+            }
+        }
+        theta[tid] = th;
+    };
+
+    int ph = 0;
+    const int64_t j_lo = sl * NJ / S, j_hi = (sl + 1) * NJ / S;
+    for (int64_t J = j_lo; J < j_hi; ++J) {
+        jn_i32x4 acc[4][4];
+        block_mma(lds, a, b, I, J, KB, acc);
+
+        int64_t jrow[4];
+        jn_f32x4 ys[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            jrow[c] = (J * JB_TILES + wb * 4 + c) * 16 + col;
+            ys[c] = jrow[c] < nb ? sb[jrow[c]] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        uint64_t mask = 0;                                       // bit (r * 4 + e) * 4 + c: l above the row's theta as it was
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = (wa * 4 + r) * 16 + g4 + e;
+                if (I * JB_ROWS + row >= na) continue;
+                const float t = theta[row];
+                const jn_f32x4 xs = sx[row];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (jrow[c] >= nb) continue;
+                    if (knn_lower(acc[r][c][e], xs, ys[c], c0) > t) mask |= 1ull << ((r * 4 + e) * 4 + c);
+                }
+            }
+        }
+        // steps [lo, hi) of (r, e) into the queue of phase p; a position beyond the queue is counted and dropped
+        auto push = [&](int lo, int hi, int p) {
+            const uint64_t mm = hi - lo == 16 ? mask : mask & (((1ull << (4 * (hi - lo))) - 1) << (4 * lo));
+            const uint32_t mine = (uint32_t)__popcll(mm);
+            if (!__any(mine != 0)) return;                       // wave-uniform
+            const uint32_t incl = wave_inclusive_sum(mine);
+            const uint32_t total = __shfl(incl, 63, 64);
+            uint32_t base = 0;
+            if (lane == 63) base = atomicAdd(&qn[p], total);
+            base = __shfl(base, 63, 64);
+            uint32_t pos = base + (incl - mine);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if ((mm >> ((r * 4 + e) * 4 + c)) & 1) {
+                            if (pos < KNN_QCAP) {
+                                const int row = (wa * 4 + r) * 16 + g4 + e;
+                                qrow[pos] = (uint32_t)row;
+                                qval[pos] = knn_lower(acc[r][c][e], sx[row], ys[c], c0);
+                            }
+                            ++pos;
+                        }
+        };
+        // after a phase: merge what it queued, clear the idle counter (last read before the previous such barrier), swap
+        auto settle = [&](uint32_t n, bool fits) {
+            if (fits) merge(n < KNN_QCAP ? n : KNN_QCAP);
+            if (tid == 0) qn[ph ^ 1] = 0;
+            __syncthreads();
+            ph ^= 1;
+        };
+        push(0, 16, ph);
+        __syncthreads();                                         // the queue is whole; every wave has left the staging buffers
+        uint32_t n = qn[ph];
+        if (n == 0) continue;                                    // uniform: nothing was queued, no list changed
+        if (n <= KNN_QCAP) {
+            settle(n, true);
+            continue;
+        }
+        settle(n, false);
+        for (int step = 0; step < 16; ++step) {
+            push(step, step + 1, ph);
+            __syncthreads();
+            n = qn[ph];
+            settle(n, n != 0);                                   // always: the next step adds to a counter nobody still reads
+        }
+    }
+
+    // the lists leave sorted: larger first, -inf behind what a list holds
+    const int64_t irow = I * JB_ROWS + tid;
+    if (tid < JB_ROWS && irow < na) {
+        float *l = top + tid * KNN_LD;
+        for (int i = 1; i < cnt; ++i) {
+            const float v = l[i];
+            int j = i;
+            for (; j > 0 && l[j - 1] < v; --j) l[j] = l[j - 1];
+            l[j] = v;
+        }
+        float *dst = lists + ((int64_t)sl * m + (irow - I0 * JB_ROWS)) * k;
+        for (int c = 0; c < k; ++c) dst[c] = c < cnt ? l[c] : ninf;
+    }
+}
+
+// t[row] = the k-th largest of the union of the row's S sorted lists (one wave per row, lane = list: k pops of the largest head)
+__global__ __launch_bounds__(256) void knn_select_kernel(const float *__restrict__ lists, int64_t m, int S, int k, float *__restrict__ t)
+{
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= m) return;                                        // wave-uniform
+    const float ninf = -__builtin_inff();
+    const float *l = lists + ((int64_t)lane * m + row) * k;
+    int ptr = 0;
+    float head = lane < S ? l[0] : ninf, kth = ninf;
+    for (int i = 0; i < k; ++i) {
+        kth = wave_max(head);
+        const uint64_t who = __ballot(head == kth);
+        if (lane == __builtin_ctzll(who)) {
+            ++ptr;
+            head = lane < S && ptr < k ? l[ptr] : ninf;
+        }
+    }
+    if (lane == 0) t[row] = kth;
+}
+
 // ---------------------------------------------------------------- exact stage
 
 constexpr int EX_TC = 64;              // candidates per workgroup: one per lane of wave 0
@@ -238,7 +460,9 @@ __device__ __forceinline__ jn_f32x4 piece(const float *rows, int64_t id, int64_t
     return v;
 }
 
-// sorted candidates (i << 32 | j) -> key (i - m_lo) << 32 | desc_key(chain) for a hit, ~0 otherwise; idx = position
+// sorted candidates (i << 32 | j) -> key (i - m_lo) << 32 | desc_key(chain) for a hit, ~0 otherwise; idx = position.  ALL (the kNN
+// join): no threshold, every candidate is kept, a NaN chain too (desc_key ranks it last in its row)
+template <bool ALL>
 __global__ __launch_bounds__(256) void exact_kernel(const float *__restrict__ ra, int64_t lda, const float *__restrict__ rb, int64_t ldb, int64_t d,
                                                     const uint64_t *__restrict__ cand, int64_t P, float tau, int64_t m_lo, bool vec,
                                                     float *__restrict__ score, uint64_t *__restrict__ key, int32_t *__restrict__ idx)
@@ -302,7 +526,7 @@ __global__ __launch_bounds__(256) void exact_kernel(const float *__restrict__ ra
     const int64_t p = c0 + lane;
     if (wave == 0 && p < P) {
         const uint64_t kk = cand[p];
-        const bool hit = acc >= tau;                             // NaN: never a hit
+        const bool hit = ALL || acc >= tau;                      // NaN: never a hit of a threshold
         score[p] = acc;
         key[p] = hit ? ((uint64_t)((int64_t)(kk >> 32) - m_lo) << 32) | desc_key(acc) : ~0ull;
         idx[p] = (int32_t)p;
@@ -402,6 +626,26 @@ __global__ __launch_bounds__(256) void offsets_kernel(const uint64_t *__restrict
         else hi = mid;
     }
     offsets[r] = lo;
+}
+
+// the first k of every row's sorted candidates into dense [m, k]; id -1 / NaN where a row has fewer; counts[r] = its candidates
+__global__ __launch_bounds__(256) void knn_dense_kernel(const int32_t *__restrict__ idx, const uint64_t *__restrict__ cand,
+                                                        const float *__restrict__ vals, const int64_t *__restrict__ offsets, int64_t m, int64_t k,
+                                                        int64_t *__restrict__ ids, float *__restrict__ scores, int32_t *__restrict__ counts)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= m * k) return;
+    const int64_t r = e / k, c = e % k;
+    const int64_t lo = offsets[r], have = offsets[r + 1] - lo;
+    if (c == 0) counts[r] = (int32_t)have;
+    if (c < have) {
+        const int32_t q = idx[lo + c];
+        ids[e] = (int64_t)(cand[q] & 0xFFFFFFFFu);
+        scores[e] = vals[q];
+    } else {
+        ids[e] = -1;
+        scores[e] = __builtin_nanf("");
+    }
 }
 
 int key_bits(int64_t m)                 // bits of the row field that keep ~0 (non-hits) above every row < m
@@ -553,18 +797,176 @@ int mdx_join_candidates(const mdx_index *a, const float *stats_a, const mdx_inde
         for (int64_t g = I0; g < I1; g += J_GROUP) {             // one launch per group of J_GROUP I blocks: J >= g only
             const int64_t blocks = J_GROUP * (NJ - g);
             MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
-            hipLaunchKernelGGL(join_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
-                               (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, g, std::min(g + J_GROUP, I1), NJ, J_GROUP, tau, c0,
-                               pairs, capacity, (unsigned long long *)count);
+            hipLaunchKernelGGL((join_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
+                               (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, g, std::min(g + J_GROUP, I1), NJ, J_GROUP, tau,
+                               (const float *)nullptr, c0, pairs, capacity, (unsigned long long *)count);
         }
     } else {
         const int64_t gs = std::min(I1 - I0, (int64_t)J_GROUP);    // a range search of <= 128 queries is one block row
         const int64_t blocks = ceil_div(I1 - I0, gs) * gs * NJ;
         MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
-        hipLaunchKernelGGL(join_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
-                           (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, I0, I1, NJ, (int)gs, tau, c0, pairs, capacity,
-                           (unsigned long long *)count);
+        hipLaunchKernelGGL((join_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
+                           (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, I0, I1, NJ, (int)gs, tau, (const float *)nullptr, c0, pairs,
+                           capacity, (unsigned long long *)count);
     }
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+// the shards, sizes and launch geometry that mdx_knn_bounds and mdx_join_candidates_rows share
+struct JoinArgs {
+    const void *ta, *tb;
+    int64_t na, nb, d, I0, I1, NJ;
+    int KB;
+    float c0;
+};
+
+int join_args(const char *who, const mdx_index *a, const mdx_index *b, int64_t a_lo, int64_t a_hi, JoinArgs *g)
+{
+    const float *sca = nullptr, *scb = nullptr;
+    int64_t rta = 0, kba = 0, rtb = 0, kbb = 0, db = 0;
+    MDX_CHECK_ARG(i8_view(a, &g->ta, &sca, &g->na, &rta, &kba) && i8_view(b, &g->tb, &scb, &g->nb, &rtb, &kbb),
+                  "%s: int8 shards are needed (an fp16 or fp32 one has no bound)", who);
+    (void)mdx_index_info(a, nullptr, &g->d, nullptr, nullptr);
+    (void)mdx_index_info(b, nullptr, &db, nullptr, nullptr);
+    MDX_CHECK_ARG(g->d == db, "%s: dimensions %lld and %lld differ", who, (long long)g->d, (long long)db);
+    MDX_CHECK_ARG(g->na < (1ll << 31) && g->nb < (1ll << 31), "%s: n >= 2^31", who);
+    MDX_CHECK_ARG(a_lo >= 0 && a_lo < a_hi && a_hi <= g->na && a_lo % JB_ROWS == 0,
+                  "%s: rows [%lld, %lld) of A: 0 <= lo < hi <= n=%lld and lo a multiple of %d", who, (long long)a_lo, (long long)a_hi,
+                  (long long)g->na, JB_ROWS);
+    g->I0 = a_lo / JB_ROWS;
+    g->I1 = ceil_div(a_hi, (int64_t)JB_ROWS);
+    g->NJ = ceil_div(g->nb, (int64_t)JB_ROWS);
+    g->KB = (int)kba;
+    g->c0 = (float)((double)(g->d + 2) * 0x1p-149);             // exact: a multiple of 2^-149 below 2^-126
+    return MDX_OK;
+}
+
+// the compute units of the current device (256 where there is none to ask: a size function called on a host without a GPU)
+int device_cus()
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
+        (void)hipGetLastError();
+        return 256;
+    }
+    return cus;
+}
+
+// slices of the J blocks per A block: 0 = as many as bring a chunk to the two workgroups per CU that the kernel's LDS allows on
+// the current device; never more than the J blocks (every slice sweeps at least one).  Every slicing gives the same bits.
+int knn_slices(int64_t m, int64_t nb, int64_t slices)
+{
+    const int64_t rb = ceil_div(m, (int64_t)JB_ROWS), NJ = ceil_div(nb, (int64_t)JB_ROWS);
+    int64_t s = slices > 0 ? slices : ceil_div((int64_t)2 * device_cus(), rb);
+    return (int)std::max((int64_t)1, std::min(std::min(s, (int64_t)KNN_MAX_SLICES), NJ));
+}
+
+int64_t mdx_knn_bounds_workspace(int64_t m, int64_t k, int64_t nb, int64_t slices)
+{
+    if (m < 1 || nb < 1 || k < 1 || k > KNN_MAX_K || k > nb || slices < 0 || slices > KNN_MAX_SLICES || m > J_MAX_ITEMS || nb > J_MAX_ITEMS)
+        return 0;
+    return round_up((int64_t)knn_slices(m, nb, slices) * m * k * (int64_t)sizeof(float), 256);
+}
+
+int mdx_knn_bounds(const mdx_index *a, const float *stats_a, const mdx_index *b, const float *stats_b, int64_t a_lo, int64_t a_hi, int64_t k,
+                   int64_t slices, float *t, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    MDX_CHECK_ARG(a && stats_a && b && stats_b && t, "mdx_knn_bounds: NULL pointer");
+    MDX_CHECK_ARG((((uintptr_t)stats_a | (uintptr_t)stats_b) & 15) == 0, "mdx_knn_bounds: stats_a / stats_b must be 16-byte aligned");
+    MDX_CHECK_ARG(k >= 1 && k <= KNN_MAX_K, "mdx_knn_bounds: k=%lld must be in [1, MDX_KNN_JOIN_MAX_K = %d]", (long long)k, KNN_MAX_K);
+    MDX_CHECK_ARG(slices >= 0 && slices <= KNN_MAX_SLICES, "mdx_knn_bounds: slices=%lld must be 0 (automatic) or in [1, %d]", (long long)slices,
+                  KNN_MAX_SLICES);
+    JoinArgs g;
+    if (const int rc = join_args("mdx_knn_bounds", a, b, a_lo, a_hi, &g)) return rc;
+    MDX_CHECK_ARG(k <= g.nb, "mdx_knn_bounds: k=%lld > the %lld rows of B", (long long)k, (long long)g.nb);
+    const int64_t m = a_hi - a_lo, need = mdx_knn_bounds_workspace(m, k, g.nb, slices);
+    if (!workspace || workspace_bytes < need) {
+        set_error("mdx_knn_bounds: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_bounds");
+    const int S = knn_slices(m, g.nb, slices);
+    const int64_t gs = std::min(g.I1 - g.I0, (int64_t)J_GROUP);
+    const int64_t blocks = ceil_div(g.I1 - g.I0, gs) * gs * S;
+    MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_knn_bounds: too many blocks for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(knn_bound_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)g.ta, (const jn_f32x4 *)stats_a, a_hi,
+                       (const jn_i32x4 *)g.tb, (const jn_f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)gs, S, (int)k, g.c0,
+                       (float *)workspace, m);
+    hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)ceil_div(m, (int64_t)4)), dim3(256), 0, s, (const float *)workspace, m, S, (int)k, t);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int mdx_join_candidates_rows(const mdx_index *a, const float *stats_a, const mdx_index *b, const float *stats_b, int64_t a_lo, int64_t a_hi,
+                             const float *tau, uint64_t *pairs, int64_t capacity, int64_t *count, void *stream)
+{
+    MDX_CHECK_ARG(a && stats_a && b && stats_b && tau && pairs && count, "mdx_join_candidates_rows: NULL pointer");
+    MDX_CHECK_ARG((((uintptr_t)stats_a | (uintptr_t)stats_b) & 15) == 0, "mdx_join_candidates_rows: stats_a / stats_b must be 16-byte aligned");
+    MDX_CHECK_ARG(capacity >= 0, "mdx_join_candidates_rows: capacity=%lld < 0", (long long)capacity);
+    JoinArgs g;
+    if (const int rc = join_args("mdx_join_candidates_rows", a, b, a_lo, a_hi, &g)) return rc;
+    const int64_t gs = std::min(g.I1 - g.I0, (int64_t)J_GROUP);
+    const int64_t blocks = ceil_div(g.I1 - g.I0, gs) * gs * g.NJ;
+    MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates_rows: too many blocks for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    MDX_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL((join_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)g.ta, (const jn_f32x4 *)stats_a, a_hi,
+                       (const jn_i32x4 *)g.tb, (const jn_f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)gs, 0.f, tau, g.c0, pairs, capacity,
+                       (unsigned long long *)count);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
+}
+
+int64_t mdx_knn_resolve_workspace(int64_t P, int64_t m)
+{
+    if (P < 1 || m < 1 || P > J_MAX_ITEMS || m > J_MAX_ITEMS) return 0;
+    Carve cv{nullptr};
+    uint64_t *cs, *key, *key2;
+    int32_t *idx, *idx2;
+    float *score;
+    void *tmp;
+    size_t tb;
+    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
+    cv.take<int64_t>(m + 1);
+    return cv.used + 256;
+}
+
+int mdx_knn_resolve(const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs, int64_t P,
+                    int64_t m_lo, int64_t m, int64_t k, int64_t *ids, float *scores, int32_t *counts, void *workspace, int64_t workspace_bytes,
+                    void *stream)
+{
+    MDX_CHECK_ARG(rows_a && rows_b && pairs && ids && scores && counts, "mdx_knn_resolve: NULL pointer");
+    MDX_CHECK_ARG(P >= 1 && m >= 1 && d >= 1, "mdx_knn_resolve: P=%lld m=%lld d=%lld must be >= 1", (long long)P, (long long)m, (long long)d);
+    MDX_CHECK_ARG(P <= J_MAX_ITEMS && m <= J_MAX_ITEMS, "mdx_knn_resolve: P=%lld or m=%lld >= 2^31", (long long)P, (long long)m);
+    MDX_CHECK_ARG(k >= 1 && k <= KNN_MAX_K, "mdx_knn_resolve: k=%lld must be in [1, MDX_KNN_JOIN_MAX_K = %d]", (long long)k, KNN_MAX_K);
+    MDX_CHECK_ARG(lda >= d && ldb >= d, "mdx_knn_resolve: lda=%lld / ldb=%lld < d=%lld", (long long)lda, (long long)ldb, (long long)d);
+    MDX_CHECK_ARG(m_lo >= 0, "mdx_knn_resolve: m_lo=%lld < 0", (long long)m_lo);
+    const int64_t need = mdx_knn_resolve_workspace(P, m);
+    if (!workspace || workspace_bytes < need) {
+        set_error("mdx_knn_resolve: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
+        return MDX_ERR_WORKSPACE;
+    }
+    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_resolve");
+    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};
+    uint64_t *cs, *key, *key2;
+    int32_t *idx, *idx2;
+    float *score;
+    void *tmp;
+    size_t tb;
+    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
+    int64_t *offsets = cv.take<int64_t>(m + 1);
+    hipStream_t s = (hipStream_t)stream;
+    // as mdx_join_resolve, with no threshold: (i, j) order, the chains, the stable (row, desc_key) sort, then the first k per row
+    MDX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tb, pairs, cs, (int)P, 0, 64, s));
+    const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
+    hipLaunchKernelGGL(exact_kernel<true>, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
+                       (const uint64_t *)cs, P, 0.f, m_lo, vec, score, key, idx);
+    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
+    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, P, m, offsets);
+    hipLaunchKernelGGL(knn_dense_kernel, dim3((unsigned)ceil_div(m * k, (int64_t)256)), dim3(256), 0, s, (const int32_t *)idx2,
+                       (const uint64_t *)cs, (const float *)score, (const int64_t *)offsets, m, k, ids, scores, counts);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }
@@ -609,7 +1011,7 @@ int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int6
     // candidates in (i, j) order: the chains then run row-grouped, and the stable sort below breaks ties by ascending j
     MDX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tb, pairs, cs, (int)P, 0, 64, s));
     const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
-    hipLaunchKernelGGL(exact_kernel, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
+    hipLaunchKernelGGL(exact_kernel<false>, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
                        (const uint64_t *)cs, P, tau, m_lo, vec, score, key, idx);
     MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
     hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(256), 0, s, (const uint64_t *)key2, (const int32_t *)idx2, P, (const uint64_t *)cs,

@@ -821,6 +821,109 @@ def join_resolve(rows_a, rows_b, pairs, threshold, m_lo, m):
     return offsets, ids[:hits], scores[:hits]
 
 
+# ------------------------------------------------------------- exact kNN join
+
+KNN_JOIN_MAX_K = 64               # include/mdx.h MDX_KNN_JOIN_MAX_K: the k largest bounds of 128 rows are kept in LDS
+KNN_MAX_SLICES = 64
+
+
+def _join_operands(who, a, stats_a, b, stats_b, a_lo, a_hi):
+    for name, ix in (("a", a), ("b", b)):
+        if not isinstance(ix, DescriptorIndex) or ix._h is None:
+            raise ValueError("%s: %s must be an open DescriptorIndex" % (who, name))
+        if ix.storage != "i8":
+            raise ValueError("%s: pruning needs int8 indexes (%s is %s)" % (who, name, ix.storage))
+    if a.d != b.d:
+        raise ValueError("%s: dimensions %d and %d differ" % (who, a.d, b.d))
+    a_hi = a.n if a_hi is None else int(a_hi)
+    a_lo = int(a_lo)
+    if not (0 <= a_lo < a_hi <= a.n) or a_lo % JOIN_BLOCK:
+        raise ValueError("%s: rows [%d, %d) of %d, the first a multiple of %d" % (who, a_lo, a_hi, a.n, JOIN_BLOCK))
+    for name, st, ix in (("stats_a", stats_a, a), ("stats_b", stats_b, b)):
+        _dev(st, torch.float32, name)
+        if tuple(st.shape) != (ix.n, 4):
+            raise ValueError("%s must be join_stats of its index: [%d, 4]" % (name, ix.n))
+    return a_lo, a_hi
+
+
+def _knn_k(who, k, nb=None):
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("%s: k must be an integer >= 1, got %r" % (who, k))
+    if k > KNN_JOIN_MAX_K:
+        raise ValueError("%s: k=%d, at most KNN_JOIN_MAX_K = %d neighbours per row" % (who, k, KNN_JOIN_MAX_K))
+    if nb is not None and k > nb:
+        raise ValueError("%s: k=%d > the %d rows of b" % (who, k, nb))
+    return k
+
+
+def knn_bounds(a, stats_a, b, stats_b, lo, hi, k, slices=0):
+    """fp32 ``[hi - lo]``: the thresholds ``t_i`` of the exact kNN join (``mdx_knn_bounds``, include/mdx.h "exact kNN join") of
+    rows ``[lo, hi)`` of int8 index ``a`` against every row of ``b`` -- a lower bound of each row's exact k-th score, the k-th
+    largest of its per-pair lower bounds (-inf where fewer than k pairs have one).  ``slices``: 0 = automatic, or 1 .. 64
+    slices of b's row blocks per block of a; every value gives the same bits."""
+    lo, hi = _join_operands("knn_bounds", a, stats_a, b, stats_b, lo, hi)
+    k = _knn_k("knn_bounds", k, b.n)
+    if isinstance(slices, bool) or not isinstance(slices, int) or not 0 <= slices <= KNN_MAX_SLICES:
+        raise ValueError("knn_bounds: slices must be 0 (automatic) or an integer in [1, %d], got %r" % (KNN_MAX_SLICES, slices))
+    h = _lib.lib()
+    t = torch.empty(hi - lo, dtype=torch.float32, device=a.device)
+    ws = _workspace(h.mdx_knn_bounds_workspace(hi - lo, k, b.n, slices), a.device)
+    with _on(t):
+        check(h.mdx_knn_bounds(a._h, _vp(stats_a.data_ptr()), b._h, _vp(stats_b.data_ptr()), lo, hi, k, slices, _vp(t.data_ptr()),
+                               _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_knn_bounds")
+    return t
+
+
+def join_candidates_rows(a, stats_a, b, stats_b, taus, a_lo=0, a_hi=None, capacity=1 << 20):
+    """:func:`join_candidates` (not symmetric) with the threshold of row i read from ``taus`` (fp32 ``[a_hi - a_lo]`` on the
+    device; -inf or NaN keeps every pair of the row) (``mdx_join_candidates_rows``): ``(pairs, count)`` as there.  Synchronises
+    the stream (reads the count)."""
+    a_lo, a_hi = _join_operands("join_candidates_rows", a, stats_a, b, stats_b, a_lo, a_hi)
+    tp = _dev(taus, torch.float32, "taus")
+    if taus.dim() != 1 or taus.shape[0] != a_hi - a_lo or not taus.is_contiguous():
+        raise ValueError("taus must be a contiguous [%d] tensor, one threshold per row" % (a_hi - a_lo))
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= _MAX_ITEMS:
+        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
+    pairs = torch.empty(max(capacity, 1), dtype=torch.int64, device=a.device)
+    count = torch.zeros(1, dtype=torch.int64, device=a.device)
+    with _on(pairs):
+        check(_lib.lib().mdx_join_candidates_rows(a._h, _vp(stats_a.data_ptr()), b._h, _vp(stats_b.data_ptr()), a_lo, a_hi, tp,
+                                                  _vp(pairs.data_ptr()), capacity, _vp(count.data_ptr()), _stream()),
+              "mdx_join_candidates_rows")
+    c = int(count.item())
+    return pairs[:min(c, capacity)], c
+
+
+def knn_resolve(rows_a, rows_b, pairs, m_lo, m, k):
+    """``(ids int64 [m, k], scores fp32 [m, k], counts int32 [m])``: the exact chains of the candidate ``pairs`` (int64
+    ``i << 32 | j``, unique, rows i in ``[m_lo, m_lo + m)``) of ``rows_a`` x ``rows_b`` and the first ``k`` of every row in rank
+    order (``mdx_knn_resolve``); ``counts``: the candidates of each row -- where that is below k (thresholds that were not
+    :func:`knn_bounds`') the tail is id -1 / score NaN."""
+    ap, lda = _rows(rows_a, "rows_a")
+    bp, ldb = _rows(rows_b, "rows_b")
+    if rows_a.shape[1] != rows_b.shape[1]:
+        raise ValueError("rows_a and rows_b differ in dimension")
+    d = rows_a.shape[1]
+    m, m_lo = int(m), int(m_lo)
+    if m < 1 or m_lo < 0 or m > _MAX_ITEMS:
+        raise ValueError("knn_resolve: m=%d must be in [1, 2^31) and m_lo=%d >= 0" % (m, m_lo))
+    k = _knn_k("knn_resolve", k)
+    _dev(pairs, torch.int64, "pairs")
+    P = pairs.numel()
+    if not 1 <= P <= _MAX_ITEMS:
+        raise ValueError("knn_resolve: %d pairs, between 1 and 2^31 - 1 per call" % P)
+    dev = rows_a.device
+    h = _lib.lib()
+    ws = _workspace(h.mdx_knn_resolve_workspace(P, m), dev)
+    ids = torch.empty((m, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((m, k), dtype=torch.float32, device=dev)
+    counts = torch.empty(m, dtype=torch.int32, device=dev)
+    with _on(rows_a):
+        check(h.mdx_knn_resolve(ap, lda, bp, ldb, d, _vp(pairs.data_ptr()), P, m_lo, m, k, _vp(ids.data_ptr()), _vp(scores.data_ptr()),
+                                _vp(counts.data_ptr()), _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_knn_resolve")
+    return ids, scores, counts
+
+
 def range_select(scores, threshold, diag=None, capacity=None):
     """``(offsets int64 [m + 1], ids int64 [hits], scores fp32 [hits])``: the deterministic threshold compaction of an fp32 score
     matrix ``[m, n]`` (rows contiguous, any stride) into the CSR of include/mdx.h (``mdx_range_select``): hits ``s >= threshold``,

@@ -12,9 +12,9 @@ import math
 
 import torch
 
-from . import _lib, ops
-
-DBA_MEMORY_CAP = 4 << 30        # bytes of [chunk, N] scores + top-k workspace one DBA chunk may hold
+from . import _lib, ops, search
+from .search import KNN_MEMORY_CAP as DBA_MEMORY_CAP        # bytes of [chunk, N] scores + top-k workspace one DBA chunk may hold
+from .search import _knn_bytes as _dba_bytes
 
 
 def _check(k, alpha):
@@ -54,28 +54,30 @@ def query_expansion(qvecs, vecs, k, alpha, index=None, compute="chain"):
     return _similarity(vecs, expanded, index, compute, out=scores), expanded
 
 
-def _dba_bytes(n, chunk, k):
-    return chunk * n * 4 + ops.rank_workspace_bytes(n, chunk) + chunk * k * 12
-
-
 def dba_chunk(n, k, cap=DBA_MEMORY_CAP):
     """Rows per DBA step: as many as keep the ``[chunk, N]`` scores, the top-k workspace and the neighbour lists under
-    ``cap`` bytes (at least one)."""
-    chunk = max(1, min(n, cap // max(1, _dba_bytes(n, 1, k))))
-    while chunk > 1 and _dba_bytes(n, chunk, k) > cap:
-        chunk = max(1, min(chunk - 1, chunk * cap // _dba_bytes(n, chunk, k)))
-    return chunk
+    ``cap`` bytes (at least one) -- :func:`search.knn_chunk`."""
+    return search.knn_chunk(n, k, cap)
 
 
-def database_augmentation(vecs, k, alpha, chunk=None, layout="ND"):
+def _neighbours(vecs, k, chunk, index):
+    """The exact top-k lists of every row: :func:`search.knn_join` (the exact route, or pruned on an int8 ``index`` of ``vecs``)."""
+    if index is not None and (not isinstance(index, ops.DescriptorIndex) or index.storage != "i8"):
+        raise ValueError("index must be an int8 DescriptorIndex of vecs (storage='i8'), or None for the exact route")
+    res = search.knn_join(index, vecs, k, chunk=chunk)
+    return res.ids, res.scores
+
+
+def database_augmentation(vecs, k, alpha, chunk=None, layout="ND", index=None):
     """DBA of the database ``vecs``: a NEW ``[N, D]`` row-major fp32 matrix whose row i is
     ``knn_aggregate(X, topk(x_i.X^T, min(k, N)), alpha)`` with no separate self term (the top-k includes i itself), always
     read from the original rows.  ``vecs`` is never written.
 
-    The exact fp32 chain, ``chunk`` rows at a time (scores_rowmajor, topk, knn_aggregate into the preallocated result);
-    the default chunk keeps each step under ``DBA_MEMORY_CAP`` bytes (:func:`dba_chunk`).  The result does not depend on
-    the chunk: the similarity and the top-k of a row do not depend on the other rows of the launch.  ``layout="DN"``
-    accepts the reference's ``[D, N]`` matrix through one transpose copy; the result is ``[N, D]`` either way."""
+    The neighbour lists are :func:`search.knn_join`'s: the exact fp32 chain, ``chunk`` rows at a time (scores_rowmajor, topk;
+    the default chunk keeps each step under ``DBA_MEMORY_CAP`` bytes, :func:`dba_chunk`), or, with ``index`` -- an int8
+    ``DescriptorIndex`` of ``vecs`` -- the same lists pruned on the int8 shard; then one ``knn_aggregate``.  The result depends
+    on neither the chunk nor the index.  ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy
+    (an ``index`` is of the row-major rows); the result is ``[N, D]`` either way."""
     _check(k, alpha)
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):
         raise ValueError("chunk must be an integer >= 1, got %r" % (chunk,))
@@ -87,22 +89,12 @@ def database_augmentation(vecs, k, alpha, chunk=None, layout="ND"):
         raise ValueError("vecs must be 2-d, got %s" % (tuple(vecs.shape),))
     n, d = vecs.shape
     k = min(k, n)
-    chunk = min(chunk or dba_chunk(n, k), n)
-    # the exact chain on the rows where they lie; a dimension that is not a multiple of 4 goes through an index of the same
-    # rows (same kernels, same bits: include/mdx.h mdx_scores_rowmajor)
-    index = None if d % 4 == 0 else ops.DescriptorIndex(vecs, "ND")
+    ids, sims = _neighbours(vecs, k, chunk, index)
     out = torch.empty((n, d), dtype=torch.float32, device=vecs.device)
-    scores = torch.empty((chunk, n), dtype=torch.float32, device=vecs.device)
-    workspace = ops._workspace(ops.rank_workspace_bytes(n, chunk), vecs.device)
-    try:
-        for i0 in range(0, n, chunk):
-            i1 = min(n, i0 + chunk)
-            block = _similarity(vecs, vecs[i0:i1], index, "chain", out=scores[:i1 - i0])
-            ids, sims = ops.topk(block, k, workspace=workspace)
-            ops.knn_aggregate(vecs, ids, sims, alpha, out=out[i0:i1])
-    finally:
-        if index is not None:
-            index.close()
+    step = min(chunk or dba_chunk(n, k), n)                  # the aggregation launches of the chunked loop, unchanged
+    for i0 in range(0, n, step):
+        i1 = min(n, i0 + step)
+        ops.knn_aggregate(vecs, ids[i0:i1], sims[i0:i1], alpha, out=out[i0:i1])
     return out
 
 
@@ -124,16 +116,17 @@ def _check_real(x, what, upper=None):
 
 class DiffusionGraph:
     """The normalised mutual kNN graph of the database ``vecs`` ``[N, D]`` that :func:`diffusion` solves on
-    (``mdx_knn_graph``; definition in ``include/mdx.h``).  Built once per database, like DBA: the exact fp32 chain
-    ``chunk`` rows at a time (scores_rowmajor, topk of ``min(k, N)``), under the DBA memory cap for the chunk
-    (:func:`dba_chunk`), then the graph kernel on the whole ``[N, k]`` lists.  The lists do not depend on the chunk.
+    (``mdx_knn_graph``; definition in ``include/mdx.h``).  Built once per database, like DBA: the neighbour lists of
+    :func:`search.knn_join` -- the exact fp32 chain ``chunk`` rows at a time (scores_rowmajor, topk of ``min(k, N)``), under the
+    DBA memory cap for the chunk (:func:`dba_chunk`), or pruned on ``index``, an int8 ``DescriptorIndex`` of ``vecs`` -- then
+    the graph kernel on the whole ``[N, k]`` lists.  The lists depend on neither the chunk nor the index.
 
     Attributes: ``cols`` int32 / ``vals`` fp32 ``[N, k]``, ``counts`` int32 ``[N]``, ``n``, ``k`` (``min(k, N)``),
     ``gamma``, and ``wvals`` fp32 ``[N, k]``: with ``weights=True`` the unnormalised weights that the truncated solve
     renormalises on each query's subgraph (``mdx_knn_graph_weights``, N * k * 4 more bytes), else None.
     ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy."""
 
-    def __init__(self, vecs, k=50, gamma=3.0, chunk=None, layout="ND", weights=False):
+    def __init__(self, vecs, k=50, gamma=3.0, chunk=None, layout="ND", weights=False, index=None):
         _check_int(k, "k")
         _check_real(gamma, "gamma")
         if chunk is not None:
@@ -146,23 +139,7 @@ class DiffusionGraph:
             raise ValueError("vecs must be 2-d, got %s" % (tuple(vecs.shape),))
         n, d = vecs.shape
         k = min(k, n)
-        chunk = min(chunk or dba_chunk(n, k), n)
-        index = None if d % 4 == 0 else ops.DescriptorIndex(vecs, "ND")      # same kernels, same bits (see DBA)
-        ids = torch.empty((n, k), dtype=torch.int64, device=vecs.device)
-        sims = torch.empty((n, k), dtype=torch.float32, device=vecs.device)
-        scores = torch.empty((chunk, n), dtype=torch.float32, device=vecs.device)
-        workspace = ops._workspace(ops.rank_workspace_bytes(n, chunk), vecs.device)
-        try:
-            for i0 in range(0, n, chunk):
-                i1 = min(n, i0 + chunk)
-                block = _similarity(vecs, vecs[i0:i1], index, "chain", out=scores[:i1 - i0])
-                bi, bs = ops.topk(block, k, workspace=workspace)
-                ids[i0:i1] = bi
-                sims[i0:i1] = bs
-        finally:
-            if index is not None:
-                index.close()
-        del scores, workspace
+        ids, sims = _neighbours(vecs, k, chunk, index)
         self.cols, self.vals, self.counts = ops.knn_graph(ids, sims, gamma)
         self.wvals = ops.knn_graph_weights(ids, sims, gamma)[1] if weights else None     # same cols / counts
         self.n, self.k, self.gamma = n, k, float(gamma)

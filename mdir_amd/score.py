@@ -29,7 +29,11 @@ sub-key ``truncate: R`` (``kq <= R <= 4096``; no default) solves each query on t
 single-process; not with the re-ranking keys) rescores each query's top-K rows of the compressed scores exactly
 (``ops.rescore``, the fp32 chain) and ranks by the composite: the rescored top-K, then every other row in the compressed
 order.  For int8 it prints the certified depth (``ops.rescore_certify``) per query: min / median / max.
+``neighbours: exact | i8`` (criterion key, default ``exact``; only with ``database_augmentation`` or ``diffusion``) chooses how
+their neighbour lists are built: ``i8`` prunes the all-pairs top-k on a temporary int8 index of the rows (``search.knn_join``);
+the lists, and so the results, are the same bits.
 """
+import contextlib
 import gzip
 import json
 import lzma
@@ -116,6 +120,18 @@ class CirDatasetAp:
         self.diffusion = _diffusion_params(params.pop("diffusion", None))
         if self.diffusion and self.query_expansion:
             raise ValueError("diffusion together with query_expansion is not supported: choose one")
+        # how DBA and the diffusion graph get their neighbour lists: "exact" (fp32 scores of every pair) or "i8" (the same lists,
+        # pruned on a temporary int8 index of the rows: search.knn_join)
+        self.neighbours = params.pop("neighbours", "exact")
+        if self.neighbours not in ("exact", "i8"):
+            raise ValueError("neighbours: 'exact' or 'i8', got %r" % (self.neighbours,))
+        if self.neighbours != "exact" and not (self.database_augmentation or self.diffusion):
+            raise ValueError("neighbours: %s builds the neighbour lists of database_augmentation / diffusion; neither is on"
+                             % self.neighbours)
+        for key in ("database_augmentation", "diffusion"):
+            if self.neighbours == "i8" and getattr(self, key) and getattr(self, key)["k"] > ops.KNN_JOIN_MAX_K:
+                raise ValueError("neighbours: i8 keeps at most %d neighbours per row (KNN_JOIN_MAX_K); %s has k=%d"
+                                 % (ops.KNN_JOIN_MAX_K, key, getattr(self, key)["k"]))
         # exact rescoring of a shortlist of the compressed scores (not in the reference): {shortlist: K}; None = off
         self.rescore = _rescore_params(params.pop("rescore", None))
         if self.rescore:
@@ -184,7 +200,8 @@ class CirDatasetAp:
             # split-precision modes need their own operand formats and build an index
             if self.database_augmentation:
                 with range_("database_augmentation"):               # DBA first: the queries keep their own descriptors
-                    vecs = rerank.database_augmentation(vecs, **self.database_augmentation)
+                    with _neighbour_index(vecs, self.neighbours) as nix:
+                        vecs = rerank.database_augmentation(vecs, index=nix, **self.database_augmentation)
             direct = self.storage == "f32" and self.similarity == "exact" and vecs.shape[1] % 4 == 0
             index = None if direct else ops.DescriptorIndex(vecs, "ND", storage=self.storage)
             with range_("similarity"):
@@ -200,7 +217,8 @@ class CirDatasetAp:
                 p = self.diffusion
                 with range_("diffusion"):
                     truncate = p.get("truncate")
-                    graph = rerank.DiffusionGraph(vecs, k=p["k"], gamma=p["gamma"], weights=truncate is not None)
+                    with _neighbour_index(vecs, self.neighbours) as nix:
+                        graph = rerank.DiffusionGraph(vecs, k=p["k"], gamma=p["gamma"], weights=truncate is not None, index=nix)
                     scores = rerank.diffusion(qvecs, vecs, graph, kq=p["kq"], alpha=p["alpha"], iters=p["iters"],
                                               tol=p["tol"], scores=scores, truncate=truncate)
                     graph.close()
@@ -261,6 +279,18 @@ def _rerank_params(value, key):
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
         raise ValueError("%s: alpha must be a finite number >= 0, got %r" % (key, alpha))
     return {"k": k, "alpha": float(alpha)}
+
+
+@contextlib.contextmanager
+def _neighbour_index(vecs, neighbours):
+    """The index the neighbour lists are pruned on: a temporary int8 one of ``vecs`` for ``neighbours: i8`` (closed on exit),
+    None for ``exact``."""
+    index = ops.DescriptorIndex(vecs, "ND", storage="i8") if neighbours == "i8" else None
+    try:
+        yield index
+    finally:
+        if index is not None:
+            index.close()
 
 
 def _diffusion_params(value):

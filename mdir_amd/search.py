@@ -18,6 +18,12 @@ chain score is ``>= threshold`` -- query x database row, or database row pairs i
 int8 ``index`` the join kernel prunes on the int8 scores with a per-pair error bound that can only over-select (the proof is in
 ``include/mdx.h``), and the exact chain decides every candidate; with ``index=None`` the exact route scores everything in fp32 and
 compacts.  Both routes return the same bits.
+
+``knn_join(index, rows, k)`` is the all-pairs kNN query: the exact top-k of every row against all rows (the neighbour lists of
+DBA and of the diffusion graph) as a :data:`KnnResult`.  With an int8 ``index`` each chunk of rows runs bounds -> candidates ->
+resolve (``include/mdx.h``, "exact kNN join"): a lower bound of every row's own k-th score from the int8 shard, the join kernel
+at that per-row threshold, the exact chain on the candidates.  With ``index=None`` it is the exact route, ``scores_rowmajor`` (or
+an fp32 index) + ``topk`` on chunks of rows.  Both routes return the same bits.
 """
 from collections import namedtuple
 
@@ -28,6 +34,10 @@ from . import ops
 RangeResult = namedtuple("RangeResult", ["offsets", "ids", "scores"])
 RangeResult.__doc__ = """CSR over the queries (the rows i of a self-join): offsets int64 [m + 1], ids int64 [P], scores fp32 [P]; segment q
 = ``ids[offsets[q]:offsets[q + 1]]``, larger score first, equal scores by ascending id."""
+
+KnnResult = namedtuple("KnnResult", ["ids", "scores", "pruned_rows"])
+KnnResult.__doc__ = """ids int64 [N, k], scores fp32 [N, k]: every row's exact top-k in rank order (its own match included);
+pruned_rows: the rows whose list came from the int8 route (0 on the exact route)."""
 
 SearchResult = namedtuple("SearchResult", ["ids", "scores", "certified", "fallback"])
 SearchResult.__doc__ = """ids int64 [nq, k], scores fp32 [nq, k]; certified int32 [nq] (int8 index) or None (fp16);
@@ -210,3 +220,115 @@ def self_join(index, rows, threshold, chunk=None, max_pairs=None):
         if max_pairs is not None and total > max_pairs:
             raise ValueError("self_join: more than max_pairs=%d pairs at threshold %r" % (max_pairs, threshold))
     return _concat(parts, rows.device)
+
+
+# ------------------------------------------------------------------------------------------------------ exact kNN join
+
+KNN_MEMORY_CAP = 4 << 30        # bytes of [chunk, N] scores + top-k workspace one step of the exact route may hold
+
+
+def _knn_bytes(n, chunk, k):
+    return chunk * n * 4 + ops.rank_workspace_bytes(n, chunk) + chunk * k * 12
+
+
+def knn_chunk(n, k, cap=KNN_MEMORY_CAP):
+    """Rows per step of the exact route: as many as keep the ``[chunk, N]`` scores, the top-k workspace and the neighbour
+    lists under ``cap`` bytes (at least one)."""
+    chunk = max(1, min(n, cap // max(1, _knn_bytes(n, 1, k))))
+    while chunk > 1 and _knn_bytes(n, chunk, k) > cap:
+        chunk = max(1, min(chunk - 1, chunk * cap // _knn_bytes(n, chunk, k)))
+    return chunk
+
+
+class _ExactKnn:
+    """The exact route on row ranges: ``scores_rowmajor`` where the rows lie (D % 4 == 0) or an fp32 index of the same rows
+    (same kernels, same bits: include/mdx.h mdx_scores_rowmajor), then ``topk``; the score block and the top-k workspace are
+    allocated once."""
+
+    def __init__(self, rows, k, chunk):
+        n, d = rows.shape
+        self.rows, self.k, self.chunk = rows, k, chunk
+        self.index = None if d % 4 == 0 else ops.DescriptorIndex(rows, "ND")
+        self.scores = torch.empty((chunk, n), dtype=torch.float32, device=rows.device)
+        self.workspace = ops._workspace(ops.rank_workspace_bytes(n, chunk), rows.device)
+
+    def run(self, lo, hi, ids, sims):
+        for i0 in range(lo, hi, self.chunk):
+            i1 = min(hi, i0 + self.chunk)
+            if self.index is None:
+                block = ops.scores_rowmajor(self.rows, self.rows[i0:i1], "ND", out=self.scores[:i1 - i0])
+            else:
+                block = self.index.scores(self.rows[i0:i1], "ND", out=self.scores[:i1 - i0])
+            bi, bs = ops.topk(block, self.k, workspace=self.workspace)
+            ids[i0:i1] = bi
+            sims[i0:i1] = bs
+
+    def close(self):
+        if self.index is not None:
+            self.index.close()
+        self.index = self.scores = self.workspace = None
+
+
+def _check_count(x, what):
+    if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+        raise ValueError("%s must be an integer >= 1, got %r" % (what, x))
+
+
+def knn_join(index, rows, k, chunk=None, capacity=None):
+    """The exact top-``min(k, N)`` of every row of ``rows`` (fp32 ``[N, D]`` on the device) against all of them, its own match
+    included, as a :data:`KnnResult`: the bits of ``topk(scores of the rows against an fp32 index of them, k)``.
+
+    ``index=None``: the exact route, ``chunk`` rows at a time (default: :func:`knn_chunk`, what fits ``KNN_MEMORY_CAP``).
+    ``index``: an int8 ``DescriptorIndex`` of ``rows``; per chunk (a multiple of 128 rows, default 32 768) ``knn_bounds`` ->
+    ``join_candidates_rows`` -> ``knn_resolve``.  A candidate buffer that overflows (``capacity`` pairs at first) is run again at
+    the counted size.  A chunk with more than ``chunk * N / 8`` candidates is one the bound does not prune (structureless rows:
+    at D = 2048 the bound is about 1.3 standard deviations of random scores) and takes the exact route instead;
+    ``pruned_rows`` counts the rows that stayed on the int8 route.  The bits depend on none of this."""
+    _check_rows(index, rows)
+    _check_count(k, "k")
+    if chunk is not None:
+        _check_count(chunk, "chunk")
+    if capacity is not None:
+        _check_count(capacity, "capacity")
+    n, d = rows.shape
+    k = min(k, n)
+    if index is not None and k > ops.KNN_JOIN_MAX_K:
+        raise ValueError("knn_join: k=%d with an index: the int8 route keeps at most KNN_JOIN_MAX_K = %d neighbours per row "
+                         "(pass index=None for the exact route)" % (k, ops.KNN_JOIN_MAX_K))
+    ids = torch.empty((n, k), dtype=torch.int64, device=rows.device)
+    sims = torch.empty((n, k), dtype=torch.float32, device=rows.device)
+    if index is None:
+        exact = _ExactKnn(rows, k, min(chunk or knn_chunk(n, k), n))
+        try:
+            exact.run(0, n, ids, sims)
+        finally:
+            exact.close()
+        return KnnResult(ids, sims, 0)
+    chunk = 1 << 15 if chunk is None else -(-chunk // ops.JOIN_BLOCK) * ops.JOIN_BLOCK
+    stats = _join_stats(index, rows)
+    capacity = capacity or 1 << 20
+    exact, pruned = None, 0
+    try:
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            limit = min((hi - lo) * n // 8, ops._MAX_ITEMS)      # beyond it the bound does not prune (and a call holds no more)
+            t = ops.knn_bounds(index, stats, index, stats, lo, hi, k)
+            pairs, count = ops.join_candidates_rows(index, stats, index, stats, t, lo, hi, min(capacity, max(limit, 1)))
+            if count > limit:
+                del pairs
+                if exact is None:
+                    exact = _ExactKnn(rows, k, min(knn_chunk(n, k), n))
+                exact.run(lo, hi, ids, sims)
+                continue
+            if count > pairs.numel():                            # the kernel counted on: run again at the exact size
+                pairs, count = ops.join_candidates_rows(index, stats, index, stats, t, lo, hi, count)
+            capacity = max(capacity, pairs.numel())
+            bi, bs, _ = ops.knn_resolve(rows, rows, pairs, lo, hi - lo, k)
+            del pairs
+            ids[lo:hi] = bi
+            sims[lo:hi] = bs
+            pruned += hi - lo
+    finally:
+        if exact is not None:
+            exact.close()
+    return KnnResult(ids, sims, pruned)
