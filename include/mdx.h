@@ -75,7 +75,20 @@ typedef enum mdx_layout {
 /* Storage type of a shard.  MDX_F32 is the exact path (k-ordered fp32 fma chain).  MDX_F16
  * stores descriptors (and the queries of a call) as IEEE fp16 and multiplies them on the
  * fp16 MFMA with fp32 accumulation (BASELINE.json configs[4]); scores then carry fp16 input
- * rounding (~1e-3 relative) -- a separate, looser parity contract (tests/test_gpu_f16.py). */
+ * rounding (~1e-3 relative against the fp32 scores).  What is pinned, bit for bit (tests/lattice.py,
+ * tests/test_gpu_lattice.py; tests/test_lattice_host.py states the same on the host):
+ *   - every fp32 input (a query: q - center, one fp32 subtraction) is rounded to fp16 to nearest, ties to even:
+ *     |x| >= 65520 becomes an infinity, values under fp16's normal range land on its subnormal grid 2^-24
+ *     (|x| <= 2^-25 becomes 0), and subnormal operands enter the MFMA as they are (nothing is flushed);
+ *   - the product of two fp16 values is exact, the accumulation is fp32; the order of the fp32 additions is
+ *     not part of the contract, so whenever every partial sum of the products is representable in fp32
+ *     (sum_k |q_k x_k| below 2^24 units of the operands' common power-of-two grid) the score is the exact dot
+ *     product of the rounded operands -- the same bits from both fp16 kernels and for every shape and layout;
+ *   - a score is NaN / +inf / -inf exactly where the IEEE product of the rounded operands is (0 * inf = NaN,
+ *     inf - inf = NaN), and a non-finite element changes no bit of any other row or query: the zero padding
+ *     of rows, queries and k multiplies nothing non-finite.
+ * On real-valued data the accumulation rounds; tests/test_gpu_f16.py bounds that (2e-6 against the float64
+ * product of the rounded operands for unit vectors). */
 /* MDX_I8 stores every row as int8 codes with one fp32 scale per row (a quarter of the fp32 bytes) and multiplies the codes
  * on the int8 MFMA (v_mfma_i32_16x16x64_i8), whose int32 accumulation is exact -- so, unlike fp16, every score is defined
  * to the bit:
@@ -367,7 +380,9 @@ int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *quer
  *                   bounds it by 2e-6 -- the summation-order bound bench.py holds the reference's own BLAS path to -- for
  *                   scores up to ~0.5 and by 1e-6 + 4e-6 |s| in general: at a self-match, s = 1, ANY fp32 evaluation of a
  *                   2048-term dot product is ~2e-6 from the exact value, the chain included).  fp32 range (bf16 has
- *                   fp32's exponent); an infinite operand gives NaN.
+ *                   fp32's exponent); an infinite operand gives NaN.  Pinned bit for bit: the six piece products are
+ *                   exact, so whenever every partial sum of them is representable in fp32 the score is their exact sum
+ *                   (operands of <= 16 significant bits: the exact dot product; tests/test_gpu_lattice.py).
  *   MDX_F32_SPLIT2  a second labelled mode, for when the matrix' dynamic range is ordinary (L2-normalised descriptors: the path's
  *                   own data).  Block floating point: each matrix is scaled by a power of two that brings its largest magnitude
  *                   into fp16's range (the shard's maximum is read once at mdx_index_create, the queries' by a reduction on the
@@ -377,7 +392,9 @@ int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *quer
  *                   exactly.  Worst case for unit vectors 2^-20 sum |x_k q_k| <= 1e-6 on top of fp32 accumulation; elements
  *                   more than 2^-27 below their matrix' largest lose relative precision (the bound is relative to
  *                   max|x| max|q|, not to each element -- use MDX_F32_SPLIT3 for wide-range data).  Half the matrix work of
- *                   SPLIT3: the kernel runs at its stream's speed (measured 1.4-1.55 ms against 1.92-2.1 and 2.6 for the exact chain). */
+ *                   SPLIT3: the kernel runs at its stream's speed (measured 1.4-1.55 ms against 1.92-2.1 and 2.6 for the exact chain).
+ *                   Pinned bit for bit: whenever every partial sum of the three kept piece products is representable in fp32
+ *                   the score is exactly hh + (hm + mh) / 2^11, unscaled by the exact power of two (tests/test_gpu_lattice.py). */
 typedef enum mdx_compute { MDX_F32_CHAIN = 0, MDX_F32_SPLIT3 = 1, MDX_F32_SPLIT2 = 2 } mdx_compute;
 
 /* mdx_scores with an explicit compute mode; workspace of at least mdx_scores_workspace_ex(nq, d, compute) bytes

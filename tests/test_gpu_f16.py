@@ -6,7 +6,11 @@ Looser contract than the fp32 path, stated here:
     only -> atol 2e-6;
   * against the fp32 reference scores the difference is the input rounding: <= 2e-3 for unit vectors;
   * the ranking is exactly the stable descending order of the GPU's own scores (integer work),
-    and agrees with the fp32 ranking wherever fp32 scores differ by more than the rounding bound."""
+    and agrees with the fp32 ranking wherever fp32 scores differ by more than the rounding bound.
+
+These are tolerance tests on real-valued data.  What the fp16 path does bit for bit -- round to nearest even of the inputs,
+the overflow to infinity, subnormal operands, exact scores whenever no partial sum rounds, the non-finite rules, both kernels
+at every dispatch branch -- is pinned in tests/test_gpu_lattice.py (data from tests/lattice.py, include/mdx.h MDX_F16)."""
 import numpy as np
 import pytest
 import torch
