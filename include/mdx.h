@@ -132,6 +132,18 @@ int mdx_capture_recover(void *stream);
 
 /* ---------------------------------------------------------------- extraction */
 
+/* Non-finite values.  The rule is the reference's (torch: relu(NaN) = NaN, clamp(min=eps) keeps NaN, max pooling and the mean
+ * return NaN for a window that holds one; checked against torch in tests/test_trunk_exact_host.py), because "NaN scores rank
+ * last" only works if the NaN arrives:
+ *   - a NaN input element makes NaN exactly the outputs the reference makes NaN: its own element (mdx_bn_act, x or residual;
+ *     a residual element of mdx_conv1x1_bn_act), its own pixel column over every output channel (the convolution's x), its
+ *     plane (mdx_pool_l2n / mdx_pool_multi / mdx_roipool: the regions that hold it), its descriptor (after the L2N; mdx_rmac);
+ *   - it changes no bit of any other output;
+ *   - an infinity follows IEEE arithmetic (relu(-inf) = 0, relu(+inf) = +inf, a maximum or a mean over a +inf is +inf).
+ * So ReLU is `y < 0 ? 0 : y`, GeM's clamp is `x < eps ? eps : x` (fmaxf returns the operand that is a number), and the maxima
+ * carry a "saw a NaN" flag.  Pinned by tests/test_gpu_trunk_exact.py and tests/test_gpu_tail_exact.py; the fused trunk and the
+ * module calls (MDIR_AMD_FUSED_TRUNK=1 / 0) give the same NaN mask. */
+
 /* Global pooling of a feature-map batch followed by L2 normalisation over channels.
  *   feat [B,C,H,W] row-major  ->  out [B,C]
  * Replaces `self.norm(self.pool(o))` of ImageRetrievalNet.forward
@@ -190,7 +202,16 @@ int mdx_l2n_rows(float *x, int64_t R, int64_t D, const float *bias, float eps, v
  * i.e. inference `bn(x)`, `out += identity`, `relu(out)` of a residual block (mdir_amd/backbones.py; the
  * torchvision Bottleneck/BasicBlock forward kept by cirtorch/networks/imageretrievalnet.py:172-173) as one
  * pass.  weight / bias / residual may be NULL; mean and var may both be NULL (no normalisation: with only
- * `bias` given this is the `conv bias + ReLU` of a VGG / AlexNet layer).  mean, var, weight, bias: C floats. */
+ * `bias` given this is the `conv bias + ReLU` of a VGG / AlexNet layer).  mean, var, weight, bias: C floats.
+ * In single IEEE fp32 operations (correctly rounded division and square root, one fma), so every element has ONE right value:
+ *     invstd = var    ? 1.0f / sqrtf(var[c] + eps) : 1.0f
+ *     scale  = weight ? invstd * weight[c]         : invstd
+ *     y      = fmaf(x - (mean ? mean[c] : 0.0f), scale, bias ? bias[c] : 0.0f)
+ *     y      = y + (residual ? residual : 0.0f)        (the + 0 without a residual turns a -0 into +0)
+ *     x      = relu ? (y < 0 ? 0 : y) : y              (NaN stays NaN)
+ * stated as oracle_bn_act(add_zero = 1) in oracle/chain.c; bit for bit in tests/test_gpu_trunk_exact.py: across the 1024-vector
+ * block boundary, on the scalar path (H*W % 4 != 0, or x / residual off the 16-byte grid) and on both sides of the split into
+ * launches of 65 535 planes. */
 int mdx_bn_act(float *x, const float *residual, int64_t N, int64_t C, int64_t HW, const float *mean,
                const float *var, const float *weight, const float *bias, float eps, int relu, void *stream);
 
@@ -198,11 +219,16 @@ int mdx_bn_act(float *x, const float *residual, int64_t N, int64_t C, int64_t HW
  *   out[b,co,p] = act( (sum_ci w[co,ci] * x[b,ci,p] - mean[co]) * weight[co] / sqrt(var[co] + eps) + bias[co]  (+ residual[b,co,p]) )
  * = `self.bn1(self.conv1(x))` + relu and `self.bn3(self.conv3(out)); out += identity; relu` of the torchvision Bottleneck
  * that cirtorch keeps as `features` (cirtorch/networks/imageretrievalnet.py:172-173; mdir_amd/backbones.py): the GEMM on
- * the f32 matrix cores (v_mfma_f32_32x32x2_f32), the arithmetic of mdx_bn_act applied to the accumulators on their way out.
+ * the f32 matrix cores (v_mfma_f32_32x32x2_f32), the arithmetic of mdx_bn_act applied to the accumulators on their way out:
+ *     acc = fmaf chain over ci = 0 .. Cin-1 from +0 (oracle_gemm_nt_chain(w, x[b]^T)), then the five lines of mdx_bn_act with
+ *     acc for x, except that without a residual NOTHING is added (no + 0: a -0 stays -0) -- oracle_bn_act(add_zero = 0).
  *   x [N,Cin,HW], out / residual [N,Cout,HW] (NCHW, contiguous; out must not alias x);  Cin % 16 == 0, Cout % 64 == 0
  *   wt [Cin,Cout]: the weights TRANSPOSED, made once per convolution by mdx_conv1x1_transpose_weights(w [Cout,Cin])
  *   mean/var, weight, bias, residual: optional as in mdx_bn_act.
- * Accumulation order: ci ascending from +0 (a fixed order; the library convolution's differs by fp32 rounding). */
+ * Accumulation order: ci ascending, one fma per ci from +0 (the 32x32x2 MFMA is bitwise that chain; a fixed order, the library
+ * convolution's differs by fp32 rounding).  Bit for bit in tests/test_gpu_trunk_exact.py: Cin / 16 = 1..5 and 64 steps, 1 and 3
+ * channel tiles, partial / full / full + partial groups of pixel tiles, rows off the 16-byte grid, both tile widths, all 2^5
+ * epilogue options; the same values as mdx_bn_act on the plain convolution output, and as mdx_scores of w against x[b]. */
 int mdx_conv1x1_transpose_weights(const float *w, int64_t Cout, int64_t Cin, float *wt, void *stream);
 int mdx_conv1x1_bn_act(const float *x, const float *wt, int64_t N, int64_t Cin, int64_t Cout, int64_t HW, const float *mean,
                        const float *var, const float *weight, const float *bias, float eps, const float *residual, int relu,

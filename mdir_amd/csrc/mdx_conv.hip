@@ -15,8 +15,8 @@
 // with the tile dimension contiguous -- x is [Cin][HW] already, the weights are transposed ONCE by the caller to
 // [Cin][Cout] -- so a fragment read is 32 consecutive words per k (row stride = 32 mod 64 words: the two k of a
 // step in different bank halves).  Accumulation order: ci ascending, one fma per ci from +0 (the MFMA is bitwise an fmaf
-// chain), i.e. a fixed order, not MIOpen's: results agree with the library path to fp32 rounding (tests: 2e-5 of the
-// output scale through a whole ResNet).
+// chain: tests/test_gpu_trunk_exact.py compares every bit with oracle/chain.c), i.e. a fixed order, not MIOpen's: results agree
+// with the library path to fp32 rounding (tests: 2e-5 of the output scale through a whole ResNet).
 #include <stdlib.h>
 
 #include "mdx_common.h"
@@ -159,6 +159,8 @@ __global__ __launch_bounds__(256, NT == 64 ? 3 : 2) void conv1x1_bn_act_kernel(
         __syncthreads();
     }
 
+    // (fmaxf(y, 0) would return the 0 for a NaN; one compare + select per value for both settings of `relu`: nothing is < -inf)
+    const float floor = relu ? 0.0f : -INFINITY;
     // C/D of the 32x32 MFMA: col = lane & 31 (pixel), row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (channel)
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(256, NT == 64 ? 3 : 2) void conv1x1_bn_act_kernel(
             const int64_t o = ob + (int64_t)(co0 + cl) * HW + p;
             float y = fmaf(acc[t][v] - s_mean[cl], s_scale[cl], s_shift[cl]);
             if (res) y += resv[t][v];
-            out[o] = relu ? fmaxf(y, 0.0f) : y;
+            out[o] = y < floor ? floor : y;                     // relu as y < 0 ? 0 : y: a NaN stays NaN, as in torch.relu
         }
     }
 }

@@ -27,13 +27,22 @@ __device__ __forceinline__ float pow_pos(float x, float p)
 template <int KIND, int MODE>
 __device__ __forceinline__ float pool_elem(float x, float p, float eps)
 {
-    if (KIND == MDX_POOL_GEM) return pow_pos<MODE>(fmaxf(x, eps), p);
+    if (KIND == MDX_POOL_GEM) return pow_pos<MODE>(x < eps ? eps : x, p);       // `clamp(min=eps)`: a NaN stays NaN (fmaxf would return eps)
     return x;
+}
+
+// The maximum keeps NaN out (fmaxf returns the operand that is a number) where the reference's max pooling returns NaN for a
+// plane that holds one: a lane remembers that it saw a NaN, the wave ORs the flags at the end (include/mdx.h, "Non-finite
+// values").
+__device__ __forceinline__ float max_or_nan(float wave_maximum, bool lane_saw_nan)
+{
+    return __any(lane_saw_nan) ? __builtin_nanf("") : wave_maximum;
 }
 
 // a lane's part of a plane read in 16-byte pieces: the order of the sum is the same for both vector types
 template <int KIND, int MODE, typename V4>
-__device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int HW, float p, float eps, int lane, float acc)
+__device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int HW, float p, float eps, int lane, float acc,
+                                             bool &saw_nan)
 {
     const V4 *s4 = (const V4 *)src;
     const int n4 = HW >> 2;
@@ -41,8 +50,12 @@ __device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int 
         const V4 v = s4[i];
         const float a = pool_elem<KIND, MODE>(v.x, p, eps), b = pool_elem<KIND, MODE>(v.y, p, eps);
         const float c = pool_elem<KIND, MODE>(v.z, p, eps), d = pool_elem<KIND, MODE>(v.w, p, eps);
-        if (KIND == MDX_POOL_MAC) acc = fmaxf(acc, fmaxf(fmaxf(a, b), fmaxf(c, d)));
-        else acc += (a + b) + (c + d);
+        if (KIND == MDX_POOL_MAC) {
+            acc = fmaxf(acc, fmaxf(fmaxf(a, b), fmaxf(c, d)));
+            saw_nan |= (a != a) | (b != b) | (c != c) | (d != d);
+        } else {
+            acc += (a + b) + (c + d);
+        }
     }
     return acc;
 }
@@ -53,21 +66,26 @@ __device__ __forceinline__ float pool_plane(const float *__restrict__ src, bool 
                                             int lane)
 {
     float acc = KIND == MDX_POOL_MAC ? -INFINITY : 0.0f;
+    bool saw_nan = false;
     if (wide) {
         // H*W % 4 == 0.  The plane of a sliced feature map starts at any multiple of 4 bytes; the summation order (hence
         // every bit of the result) must not depend on where the caller's tensor lies, so a plane off the 16-byte grid is
         // read in the same pieces through 16-byte loads at dword alignment
         typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-        if (((uintptr_t)src & 15) == 0) acc = pool_pieces<KIND, MODE, float4>(src, HW, p, eps, lane, acc);
-        else acc = pool_pieces<KIND, MODE, f32x4u>(src, HW, p, eps, lane, acc);
+        if (((uintptr_t)src & 15) == 0) acc = pool_pieces<KIND, MODE, float4>(src, HW, p, eps, lane, acc, saw_nan);
+        else acc = pool_pieces<KIND, MODE, f32x4u>(src, HW, p, eps, lane, acc, saw_nan);
     } else {
         for (int i = lane; i < HW; i += 64) {
             const float a = pool_elem<KIND, MODE>(src[i], p, eps);
-            if (KIND == MDX_POOL_MAC) acc = fmaxf(acc, a);
-            else acc += a;
+            if (KIND == MDX_POOL_MAC) {
+                acc = fmaxf(acc, a);
+                saw_nan |= a != a;
+            } else {
+                acc += a;
+            }
         }
     }
-    acc = KIND == MDX_POOL_MAC ? wave_max(acc) : wave_sum(acc);
+    acc = KIND == MDX_POOL_MAC ? max_or_nan(wave_max(acc), saw_nan) : wave_sum(acc);
     float r = acc;
     if (KIND != MDX_POOL_MAC) r = acc / (float)HW;
     if (KIND == MDX_POOL_GEM && MODE != 1) r = powf(r, inv_p);
@@ -342,11 +360,13 @@ __global__ __launch_bounds__(256) void roi_pool_kernel(const float *__restrict__
     for (int r = 0; r < grid.n; ++r) {
         const int i0 = grid.i0[r], j0 = grid.j0[r], rh = grid.h[r], rw = grid.w[r];
         float acc = KIND == MDX_POOL_MAC ? -INFINITY : 0.0f;
+        bool saw_nan = false;
         for (int e = lane; e < rh * rw; e += 64) {           // (the map is L2-resident after region 0)
             const float v = pool_elem<KIND, MODE>(p[(i0 + e / rw) * W + j0 + e % rw], pw, eps);
             acc = KIND == MDX_POOL_MAC ? fmaxf(acc, v) : acc + v;
+            if (KIND == MDX_POOL_MAC) saw_nan |= v != v;
         }
-        acc = KIND == MDX_POOL_MAC ? wave_max(acc) : wave_sum(acc);
+        acc = KIND == MDX_POOL_MAC ? max_or_nan(wave_max(acc), saw_nan) : wave_sum(acc);
         if (KIND != MDX_POOL_MAC) acc = acc / (float)(rh * rw);
         if (KIND == MDX_POOL_GEM && MODE != 1) acc = powf(acc, inv_p);
         if (lane == 0) regions_out[(b * grid.n + r) * C + c] = acc;

@@ -25,6 +25,9 @@ __device__ __forceinline__ void bn_coeffs(const BnArgs &a, int c, float &mean, f
     shift = a.bias ? a.bias[c] : 0.0f;
 }
 
+// torch.relu: a NaN stays NaN (fmaxf would return the 0), include/mdx.h "Non-finite values"
+__device__ __forceinline__ float relu_keep_nan(float y) { return y < 0.0f ? 0.0f : y; }
+
 // One workgroup = a run of one (image, channel) plane, so the four per-channel statistics are
 // scalar loads and no thread divides anything.  VEC = 4: planes are a multiple of 4 long and 16-B
 // aligned (float4 accesses); VEC = 1 covers odd plane sizes.  Each thread takes UNR elements, all
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(float *__restrict__ x, cons
             o.y = fmaf(v[u].y - mean, scale, shift) + (RES ? r[u].y : 0.f);
             o.z = fmaf(v[u].z - mean, scale, shift) + (RES ? r[u].z : 0.f);
             o.w = fmaf(v[u].w - mean, scale, shift) + (RES ? r[u].w : 0.f);
-            if (RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+            if (RELU) { o.x = relu_keep_nan(o.x); o.y = relu_keep_nan(o.y); o.z = relu_keep_nan(o.z); o.w = relu_keep_nan(o.w); }
             ((float4 *)x)[base + i] = o;
         }
     } else {
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void bn_act_kernel(float *__restrict__ x, cons
             const unsigned i = i0 + u * 256;
             if (i >= hw_vec) continue;
             const float o = fmaf(x[base + i] - mean, scale, shift) + (RES ? res[base + i] : 0.0f);
-            x[base + i] = RELU ? fmaxf(o, 0.f) : o;
+            x[base + i] = RELU ? relu_keep_nan(o) : o;
         }
     }
 }

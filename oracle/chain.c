@@ -60,6 +60,36 @@ void oracle_gemm_nt_chain(const float *a, const float *b, int64_t m, int64_t n,
         }
 }
 
+/* The trunk epilogue (mdx_bn_act; the way out of mdx_conv1x1_bn_act) in single IEEE
+ * fp32 operations, in the order the kernels commit to (include/mdx.h):
+ *     invstd = var    ? 1 / sqrtf(var[c] + eps) : 1
+ *     scale  = weight ? invstd * weight[c]      : invstd
+ *     y      = fmaf(acc - mean[c], scale, bias[c])            (mean, bias: 0 when NULL)
+ *     y      = residual ? y + residual : (add_zero ? y + 0 : y)
+ *     out    = relu ? (y < 0 ? 0 : y) : y                     (NaN stays NaN: torch.relu)
+ * mdx_bn_act adds +0 when there is no residual (add_zero = 1: -0 becomes +0), the
+ * convolution's epilogue does not.  -ffp-contract=off (oracle/Makefile) keeps the
+ * subtraction and the additions out of the fmaf.
+ * acc, residual, out: [n][c][hw]; mean, var, weight, bias: [c] or NULL. */
+void oracle_bn_act(const float *acc, const float *residual, const float *mean, const float *var,
+                   const float *weight, const float *bias, int64_t n, int64_t c, int64_t hw,
+                   float eps, int relu, int add_zero, float *out)
+{
+    #pragma omp parallel for schedule(static)
+    for (int64_t plane = 0; plane < n * c; ++plane) {
+        const int64_t ch = plane % c;
+        const float invstd = var ? 1.0f / sqrtf(var[ch] + eps) : 1.0f;
+        const float scale = weight ? invstd * weight[ch] : invstd;
+        const float m = mean ? mean[ch] : 0.0f, shift = bias ? bias[ch] : 0.0f;
+        for (int64_t i = plane * hw; i < (plane + 1) * hw; ++i) {
+            float y = fmaf(acc[i] - m, scale, shift);
+            if (residual) y = y + residual[i];
+            else if (add_zero) y = y + 0.0f;
+            out[i] = relu ? (y < 0.0f ? 0.0f : y) : y;
+        }
+    }
+}
+
 /* Sort key: larger score first; -0 == +0; NaN after everything (numpy's
  * argsort(-s) also puts NaN last, cirscore.py:70); ties by ascending id. */
 static inline uint32_t desc_key(float s)
