@@ -461,6 +461,34 @@ int mdx_topk(const float *scores, int64_t n, int64_t nq, int64_t k, int64_t id_o
              int64_t *top_ids, float *top_scores, void *workspace, int64_t workspace_bytes,
              void *stream);
 
+/* Which kernels a ranking call would run: host arithmetic only -- nothing is launched, no device memory is touched, nothing
+ * synchronises -- so that a test can say which route a shape pins (tests/rank_data.py) and a moved threshold is noticed.
+ * The library decides through the same two functions.  (Additions: MDX_ABI_VERSION stays, nothing that exists has changed.)
+ *
+ * mdx_rank_route: the route of mdx_rank_full / _segments (and of mdx_topk's MDX_TOPK_ROUTE_SORT, and of the candidate list of
+ * MDX_TOPK_ROUTE_SELECT with n = k + 4096) for rows of n scores on the current device, NOW:
+ *   MDX_RANK_ROUTE_SMALL   one workgroup sorts the row in LDS: n <= 8192, and only with the ordered ds_add_rtn form
+ *   MDX_RANK_ROUTE_PACKED  four tiled passes over packed words: n <= 2^24
+ *   MDX_RANK_ROUTE_KV      four tiled passes over (key word, id word)
+ * under the switches MDX_SORT_SMALL=0, MDX_SORT_NO_PACK=1 and MDX_SORT_RANK=ballot|atomic (read once per process).  The form a
+ * wave ranks with is the CACHED verdict of the one-off probe ("Conventions"): this function never runs the probe, and before
+ * any index was created or row ranked on this device -- or without a device -- the verdict is unknown and counts as ballots,
+ * as it does for a ranking call on a capturing stream.  `stream` is accepted for symmetry and not used.
+ * mdx_topk_route: the route of mdx_topk for [nq, n] scores, k and a workspace of workspace_bytes (one mdx_topk accepts):
+ *   MDX_TOPK_ROUTE_SAMPLED sampled threshold: n >= 16384, k <= 1024, 256 k <= n (MDX_NO_SAMPLED_TOPK, read per call, turns it off);
+ *                          a query that ends with fewer than k or more than 16384 candidates is answered exactly in the kernel
+ *   MDX_TOPK_ROUTE_SELECT  radix select, then mdx_rank_route(k + 4096) over the candidates: 4 (k + 4096) <= n
+ *   MDX_TOPK_ROUTE_SORT    the full ranking, trimmed in its last pass
+ * each only where its carve-up fits the workspace.  MDX_ERR_INVALID for sizes the ranking calls refuse. */
+#define MDX_RANK_ROUTE_SMALL 1
+#define MDX_RANK_ROUTE_PACKED 2
+#define MDX_RANK_ROUTE_KV 3
+#define MDX_TOPK_ROUTE_SAMPLED 1
+#define MDX_TOPK_ROUTE_SELECT 2
+#define MDX_TOPK_ROUTE_SORT 3
+int mdx_rank_route(int64_t n, void *stream);
+int mdx_topk_route(int64_t n, int64_t nq, int64_t k, int64_t workspace_bytes);
+
 /* Rank position of labelled database ids without materialising the ranking:
  *   pos[t] = #{i : score[q,i] ranks strictly before id t's score under the order above}
  * for t in [offsets[q], offsets[q+1]).  Gives compute_map (cirtorch/utils/

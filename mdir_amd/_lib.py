@@ -16,6 +16,8 @@ MDX_DIM_MAJOR, MDX_ROW_MAJOR = 0, 1
 MDX_POOL_GEM, MDX_POOL_MAC, MDX_POOL_SPOC = 0, 1, 2
 MDX_F32, MDX_F16, MDX_I8 = 0, 1, 2
 MDX_F32_CHAIN, MDX_F32_SPLIT3, MDX_F32_SPLIT2 = 0, 1, 2
+RANK_ROUTES = {1: "SMALL", 2: "PACKED", 3: "KV"}              # include/mdx.h MDX_RANK_ROUTE_*
+TOPK_ROUTES = {1: "SAMPLED", 2: "SELECT", 3: "SORT"}          # include/mdx.h MDX_TOPK_ROUTE_*
 COMPUTE = {"chain": MDX_F32_CHAIN, "exact": MDX_F32_CHAIN, "split3": MDX_F32_SPLIT3, "split2": MDX_F32_SPLIT2}
 STORAGE = {"f32": MDX_F32, "f16": MDX_F16, "i8": MDX_I8}
 POOL_KINDS = {"gem": MDX_POOL_GEM, "mac": MDX_POOL_MAC, "spoc": MDX_POOL_SPOC}
@@ -109,6 +111,8 @@ def _declare(lib):
         "mdx_rank_full": (i32, [p, i64, i64, i64, p, p, i64, p]),
         "mdx_rank_full_segments": (i32, [pp, pi64, i32, i64, i64, p, p, i64, p]),
         "mdx_topk": (i32, [p, i64, i64, i64, i64, p, p, p, i64, p]),
+        "mdx_rank_route": (i32, [i64, p]),
+        "mdx_topk_route": (i32, [i64, i64, i64, i64]),
         "mdx_rank_of": (i32, [p, i64, i64, p, p, i64, p, p, p]),
         "mdx_rank_positions": (i32, [p, i64, i64, i64, p, p, i64, p, p]),
         "mdx_gather_scores": (i32, [p, i64, i64, p, p, i64, p, p]),
@@ -155,7 +159,7 @@ def _declare(lib):
 EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac_workspace", "mdx_rmac", "mdx_roipool", "mdx_region_sum", "mdx_pool_l2n", "mdx_l2n_rows", "mdx_ms_aggregate",
            "mdx_ms_aggregate_batch", "mdx_pool_multi", "mdx_l2n_aggregate", "mdx_bn_act", "mdx_u8_to_chw", "mdx_resample_u8", "mdx_bilinear_pyramid", "mdx_jpeg_probe", "mdx_jpeg_coefficients", "mdx_jpeg_pixels",
            "mdx_index_create", "mdx_index_create_ex", "mdx_index_bytes", "mdx_index_create_in", "mdx_index_destroy", "mdx_index_info", "mdx_scores_workspace", "mdx_quantize_i8",
-           "mdx_scores", "mdx_scores_rowmajor", "mdx_scores_workspace_ex", "mdx_scores_ex", "mdx_rank_workspace", "mdx_rank_full", "mdx_rank_full_segments", "mdx_topk", "mdx_rank_of", "mdx_rank_positions",
+           "mdx_scores", "mdx_scores_rowmajor", "mdx_scores_workspace_ex", "mdx_scores_ex", "mdx_rank_workspace", "mdx_rank_full", "mdx_rank_full_segments", "mdx_topk", "mdx_rank_route", "mdx_topk_route", "mdx_rank_of", "mdx_rank_positions",
            "mdx_gather_scores", "mdx_rank_count", "mdx_knn_aggregate", "mdx_knn_graph_workspace", "mdx_knn_graph",
            "mdx_diffusion_workspace", "mdx_diffusion", "mdx_knn_graph_weights", "mdx_diffusion_truncated_workspace",
            "mdx_diffusion_truncated", "mdx_rescore_workspace", "mdx_rescore", "mdx_index_i8_bounds", "mdx_rescore_certify",

@@ -930,12 +930,45 @@ int probe_lds_order(hipStream_t s)
     return verdict;
 }
 
-static bool atomic_rank_ok(hipStream_t s)
+// MDX_SORT_RANK=ballot|atomic, read once per process: 0 ballots, 1 ds_add_rtn, -1 not forced
+static int forced_rank_form()
 {
     static const char *force = getenv("MDX_SORT_RANK");
-    if (force && !strcmp(force, "ballot")) return false;
-    if (force && !strcmp(force, "atomic")) return true;
+    if (force && !strcmp(force, "ballot")) return 0;
+    if (force && !strcmp(force, "atomic")) return 1;
+    return -1;
+}
+
+static bool atomic_rank_ok(hipStream_t s)
+{
+    const int forced = forced_rank_form();
+    if (forced >= 0) return forced == 1;
     return probe_lds_order(s) == 2;
+}
+
+// atomic_rank_ok from the CACHED verdict alone (mdx_rank_route): the probe is never run here, and no verdict yet -- no
+// device, no ranking call so far, only capturing streams so far -- counts as ballots, as it does for a capturing stream.
+static bool atomic_rank_known()
+{
+    const int forced = forced_rank_form();
+    if (forced >= 0) return forced == 1;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    return g_arank[dev].load(std::memory_order_acquire) == 2;
+}
+
+// THE statement of which kernels rank a row of n scores, given the form a wave ranks with: rank_impl launches what this
+// names and mdx_rank_route reports it.  The switches are read once per process.
+static int rank_route(int64_t n, bool arank)
+{
+    // MDX_SORT_NO_PACK=1: the (key word, id word) layout also for small n
+    static const bool no_pack = getenv("MDX_SORT_NO_PACK") && atoi(getenv("MDX_SORT_NO_PACK")) != 0;
+    // MDX_SORT_SMALL=0: the tiled passes also for short rows
+    static const bool no_small = getenv("MDX_SORT_SMALL") && atoi(getenv("MDX_SORT_SMALL")) == 0;
+    // (tests/test_gpu_rank_boundaries.py runs the table of tests/rank_data.py under each switch)
+    if (arank && n <= LS_CAP && !no_small) return MDX_RANK_ROUTE_SMALL;
+    if (n <= (1ll << 24) && !no_pack) return MDX_RANK_ROUTE_PACKED;
+    return MDX_RANK_ROUTE_KV;
 }
 
 template <int IN, int OUT, typename SEGT>
@@ -997,18 +1030,15 @@ static int rank_impl(const float *scores, int64_t n, int64_t nq, int64_t id_offs
     MDX_CHECK_WORKSPACE_ALIGNED(workspace, who);
     RankWs ws;
     carve(&ws, (char *)workspace, n, nq);
-    // MDX_SORT_NO_PACK=1: the (key word, id word) layout also for small n (tests run both)
-    static const bool no_pack = getenv("MDX_SORT_NO_PACK") && atoi(getenv("MDX_SORT_NO_PACK")) != 0;
     const bool arank = atomic_rank_ok(s);
-    // MDX_SORT_SMALL=0: the tiled passes also for short rows (tests run both)
-    static const bool no_small = getenv("MDX_SORT_SMALL") && atoi(getenv("MDX_SORT_SMALL")) == 0;
-    if (arank && n <= LS_CAP && !no_small) {
+    const int route = rank_route(n, arank);
+    if (route == MDX_RANK_ROUTE_SMALL) {
         hipLaunchKernelGGL(rank_small_kernel, dim3((unsigned)nq), dim3(LS_THREADS), 0, s, scores, seg, (int)n, id_offset, ranks, top_scores,
                            (int)klimit);
         MDX_LAUNCH_CHECK();
         return MDX_OK;
     }
-    if (n <= (1ll << 24) && !no_pack) {
+    if (route == MDX_RANK_ROUTE_PACKED) {
         sort_pass<FMT_SCORES, FMT_A>(ws, scores, n, nq, 0, id_offset, ranks, top_scores, klimit, arank, seg, s);
         sort_pass<FMT_A, FMT_B>(ws, scores, n, nq, 1, id_offset, ranks, top_scores, klimit, arank, seg, s);
         sort_pass<FMT_B, FMT_C>(ws, scores, n, nq, 2, id_offset, ranks, top_scores, klimit, arank, seg, s);
@@ -1581,6 +1611,18 @@ static int topk_sampled(const float *scores, int64_t n, int64_t nq, int64_t k, i
 }
 
 
+// THE statement of which of its three routes mdx_topk takes (mdx_topk_route reports it).  MDX_NO_SAMPLED_TOPK is read per call.
+static int topk_route(int64_t n, int64_t nq, int64_t k, int64_t workspace_bytes)
+{
+    // k <<< n (serving): sampled threshold, one pass over the scores
+    if (n >= 16384 && k <= 1024 && 256 * k <= n && sampled_workspace(n, nq) <= workspace_bytes && !getenv("MDX_NO_SAMPLED_TOPK"))
+        return MDX_TOPK_ROUTE_SAMPLED;
+    // k << n: radix select + sort of the candidates; otherwise the full ranking, trimmed in its last pass
+    if (4 * (k + SEL_CAP) <= n && carve_select(nullptr, nullptr, n, nq, k) <= workspace_bytes)
+        return MDX_TOPK_ROUTE_SELECT;
+    return MDX_TOPK_ROUTE_SORT;
+}
+
 }  // namespace mdx
 
 using namespace mdx;
@@ -1720,14 +1762,27 @@ int mdx_topk(const float *scores, int64_t n, int64_t nq, int64_t k, int64_t id_o
         return MDX_ERR_WORKSPACE;
     }
     MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_topk");
-    // k <<< n (serving): sampled threshold, one pass over the scores
-    if (n >= 16384 && k <= 1024 && 256 * k <= n && sampled_workspace(n, nq) <= workspace_bytes && !getenv("MDX_NO_SAMPLED_TOPK"))
+    const int route = topk_route(n, nq, k, workspace_bytes);
+    if (route == MDX_TOPK_ROUTE_SAMPLED)
         return topk_sampled(scores, n, nq, k, id_offset, top_ids, top_scores, workspace, (hipStream_t)stream);
-    // k << n: radix select + sort of the candidates; otherwise the full ranking, trimmed in its last pass
-    if (4 * (k + SEL_CAP) <= n && carve_select(nullptr, nullptr, n, nq, k) <= workspace_bytes)
+    if (route == MDX_TOPK_ROUTE_SELECT)
         return topk_select(scores, n, nq, k, id_offset, top_ids, top_scores, workspace, (hipStream_t)stream);
     return rank_impl(scores, n, nq, id_offset, top_ids, top_scores, k, workspace, workspace_bytes,
                      (hipStream_t)stream, "mdx_topk");
+}
+
+int mdx_rank_route(int64_t n, void *stream)
+{
+    (void)stream;           // the verdict is the device's, not the stream's; a capturing stream never settles it
+    MDX_CHECK_ARG(n > 0 && n < (1ll << 32), "mdx_rank_route: n=%lld out of range", (long long)n);
+    return rank_route(n, atomic_rank_known());
+}
+
+int mdx_topk_route(int64_t n, int64_t nq, int64_t k, int64_t workspace_bytes)
+{
+    MDX_CHECK_ARG(n > 0 && nq > 0 && n < (1ll << 32) && nq < 65536, "mdx_topk_route: bad sizes");
+    MDX_CHECK_ARG(k > 0 && k <= n, "mdx_topk_route: k=%lld out of range (n=%lld)", (long long)k, (long long)n);
+    return topk_route(n, nq, k, workspace_bytes);
 }
 
 int mdx_gather_scores(const float *scores, int64_t n, int64_t nq, const int64_t *ids,

@@ -628,6 +628,25 @@ def topk(scores, k, id_offset=0, workspace=None):
     return ids, vals
 
 
+def rank_route(n):
+    """``"SMALL"``, ``"PACKED"`` or ``"KV"``: the kernels ``rank_full`` would run now for rows of ``n`` scores on the current
+    device (``mdx_rank_route``: host arithmetic, nothing is launched).  Before anything was ranked on the device the form a
+    wave ranks with is unknown and the answer is the one for ballots: never ``"SMALL"``."""
+    rc = _lib.lib().mdx_rank_route(int(n), None)
+    check(min(rc, 0), "mdx_rank_route")
+    return _lib.RANK_ROUTES[rc]
+
+
+def topk_route(n, nq, k, workspace_bytes=None):
+    """``"SAMPLED"``, ``"SELECT"`` or ``"SORT"``: the route ``topk`` takes for ``[nq, n]`` scores and ``k`` (``mdx_topk_route``),
+    with the workspace ``topk`` itself allocates unless ``workspace_bytes`` is given."""
+    if workspace_bytes is None:
+        workspace_bytes = rank_workspace_bytes(n, nq)
+    rc = _lib.lib().mdx_topk_route(int(n), int(nq), int(k), int(workspace_bytes))
+    check(min(rc, 0), "mdx_topk_route")
+    return _lib.TOPK_ROUTES[rc]
+
+
 RESCORE_MAX_K = 4096              # include/mdx.h MDX_RESCORE_MAX_K: one query's shortlist is sorted in LDS
 
 
