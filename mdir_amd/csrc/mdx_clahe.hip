@@ -283,11 +283,7 @@ int mdx_clahe_u8_to_chw(const uint8_t *rgb, int64_t B, int64_t H, int64_t W, int
     MDX_CHECK_ARG(B > 0 && H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24) && B < 65536, "mdx_clahe_u8_to_chw: bad sizes");
     MDX_CHECK_ARG(tiles_x >= 1 && tiles_y >= 1 && tiles_x <= 256 && tiles_y <= 256 && clip_limit >= 0, "mdx_clahe_u8_to_chw: bad grid or clip limit");
     const int64_t need = mdx_clahe_workspace(B, H, W, tiles_x, tiles_y);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_clahe_u8_to_chw: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_clahe_u8_to_chw");
+    MDX_CHECK_WORKSPACE("mdx_clahe_u8_to_chw", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     uint8_t *l8 = (uint8_t *)workspace, *luts = l8 + round_up(B * H * W, 256);
     uint8_t *l8_out = luts + round_up(B * (int64_t)tiles_x * tiles_y * 256, 256);

@@ -28,9 +28,20 @@ int probe_lds_order(hipStream_t s);
         }                                         \
     } while (0)
 
-// every workspace of the ABI: 16-byte aligned (include/mdx.h, "Alignment"); the carved pieces hold 8- and 16-byte words
+// the alignment half alone (mdx_index.hip writes its size test out)
 #define MDX_CHECK_WORKSPACE_ALIGNED(ws, who) \
     MDX_CHECK_ARG((((uintptr_t)(ws)) & 15) == 0, "%s: workspace must be 16-byte aligned", who)
+
+// every workspace of the ABI: `need` bytes (MDX_ERR_WORKSPACE otherwise, for NULL too) and 16-byte aligned (include/mdx.h,
+// "Alignment"; the carved pieces hold 8- and 16-byte words).  who: the entry point, a literal or a runtime string
+#define MDX_CHECK_WORKSPACE(who, ws, bytes, need)                                                                      \
+    do {                                                                                                               \
+        if (!(ws) || (bytes) < (need)) {                                                                               \
+            ::mdx::set_error("%s: workspace %lld B < required %lld B", who, (long long)(bytes), (long long)(need));    \
+            return MDX_ERR_WORKSPACE;                                                                                  \
+        }                                                                                                              \
+        MDX_CHECK_WORKSPACE_ALIGNED(ws, who);                                                                          \
+    } while (0)
 
 #define MDX_HIP(call)                                                                   \
     do {                                                                                \
@@ -85,6 +96,20 @@ __device__ __forceinline__ float wave_max(float v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ double wave_max_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ double wave_min_d(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
     return v;
 }
 

@@ -692,11 +692,7 @@ int mdx_knn_graph(const int64_t *ids, const float *sims, int64_t n, int64_t k, f
     MDX_CHECK_ARG(k <= (1ll << 20), "mdx_knn_graph: k=%lld too large", (long long)k);
     MDX_CHECK_ARG(isfinite(gamma) && gamma >= 0.0f, "mdx_knn_graph: gamma=%g must be finite and >= 0", (double)gamma);
     const int64_t need = mdx_knn_graph_workspace(n);
-    if (workspace_bytes < need) {
-        set_error("mdx_knn_graph: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_graph");
+    MDX_CHECK_WORKSPACE("mdx_knn_graph", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     float *rinv = (float *)workspace;
     hipLaunchKernelGGL(knn_graph_edges_kernel, dim3((unsigned)ceil_div(n, DIF_WAVES)), dim3(64 * DIF_WAVES), 0, s, ids, sims,
@@ -739,11 +735,7 @@ int mdx_diffusion(const int32_t *cols, const float *vals, const int32_t *counts,
                       !overlaps(out, span, scores, ((nq - 1) * ld_scores + n) * (int64_t)sizeof(float)),
                   "mdx_diffusion: out overlaps scores (only out == scores with the same stride is allowed)");
     const int64_t need = dif_carve(nullptr, nullptr, n, nq);
-    if (workspace_bytes < need) {
-        set_error("mdx_diffusion: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "mdx_diffusion: workspace must be 16-byte aligned");
+    MDX_CHECK_WORKSPACE("mdx_diffusion", workspace, workspace_bytes, need);
     DifWs ws;
     dif_carve(&ws, (char *)workspace, n, nq);
     hipStream_t s = (hipStream_t)stream;
@@ -795,11 +787,7 @@ int mdx_knn_graph_weights(const int64_t *ids, const float *sims, int64_t n, int6
     MDX_CHECK_ARG(k <= (1ll << 20), "mdx_knn_graph_weights: k=%lld too large", (long long)k);
     MDX_CHECK_ARG(isfinite(gamma) && gamma >= 0.0f, "mdx_knn_graph_weights: gamma=%g must be finite and >= 0", (double)gamma);
     const int64_t need = mdx_knn_graph_workspace(n);
-    if (workspace_bytes < need) {
-        set_error("mdx_knn_graph_weights: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_graph_weights");
+    MDX_CHECK_WORKSPACE("mdx_knn_graph_weights", workspace, workspace_bytes, need);
     hipLaunchKernelGGL(knn_graph_edges_kernel, dim3((unsigned)ceil_div(n, DIF_WAVES)), dim3(64 * DIF_WAVES), 0,
                        (hipStream_t)stream, ids, sims, n, k, gamma, cols, w, counts, (float *)workspace);
     MDX_LAUNCH_CHECK();
@@ -842,11 +830,7 @@ int mdx_diffusion_truncated(const int32_t *cols, const float *w, const int32_t *
                       !overlaps(out, span, scores, ((nq - 1) * ld_scores + n) * (int64_t)sizeof(float)),
                   "mdx_diffusion_truncated: out overlaps scores (only out == scores with the same stride is allowed)");
     const int64_t need = mdx_diffusion_truncated_workspace(n, k, nq, r);
-    if (workspace_bytes < need) {
-        set_error("mdx_diffusion_truncated: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "mdx_diffusion_truncated: workspace must be 16-byte aligned");
+    MDX_CHECK_WORKSPACE("mdx_diffusion_truncated", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int64_t lds = trd_lds(r);
     auto solve = diffusion_truncated_solve_kernel;

@@ -469,11 +469,7 @@ int mdx_gram_f64(const double *a, int64_t d, int64_t n, const double *center, do
     MDX_CHECK_ARG(a && out, "mdx_gram_f64: NULL pointer");
     MDX_CHECK_ARG(d > 0 && n > 0 && d <= (1ll << 21) && n < (1ll << 36), "mdx_gram_f64: d=%lld n=%lld", (long long)d, (long long)n);
     const int64_t need = mdx_gram_f64_workspace(d, n);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_gram_f64: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_gram_f64");
+    MDX_CHECK_WORKSPACE("mdx_gram_f64", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int64_t ld = padded_ld(d);
     double *at = (double *)workspace, *part = (double *)((char *)workspace + transposed_bytes(n, d));
@@ -532,11 +528,7 @@ int mdx_project_f64(const double *p, int64_t dout, int64_t d, const double *x, i
     MDX_CHECK_ARG(dout > 0 && d > 0 && n > 0 && dout < (1ll << 20) && d < (1ll << 20) && n < (1ll << 36), "mdx_project_f64: dout=%lld d=%lld n=%lld",
                   (long long)dout, (long long)d, (long long)n);
     const int64_t need = mdx_project_f64_workspace(dout, d);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_project_f64: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_project_f64");
+    MDX_CHECK_WORKSPACE("mdx_project_f64", workspace, workspace_bytes, need);
     MDX_CHECK_ARG(ceil_div(dout, (int64_t)64) < 65536, "mdx_project_f64: too many tiles");
     hipStream_t s = (hipStream_t)stream;
     double *pt = (double *)workspace;

@@ -13,7 +13,8 @@
 //                         an LDS queue; knn_select_kernel takes the k-th largest of a row's slices.  join_kernel<., ROWS> then reads
 //                         its threshold per row, and knn_dense_kernel writes the first k of every row's sorted candidates.
 //   exact_kernel          one workgroup per 64 sorted candidates: the A and B row pieces are staged in LDS 128 k at a time
-//                         and wave 0 runs the k-ascending fmaf chains of mdx_rescore (lane = candidate).
+//                         and wave 0 runs the chains of mdx_rescore (lane = candidate): the row loader, the stage arithmetic
+//                         and the four-link chain step are those of mdx_exact.h, shared with rescore_kernel.
 //   select_count/_write   the dense threshold compaction of an fp32 score matrix (one workgroup per row, ordered).
 //   the final order       one stable radix sort of (row, desc_key(score)) keys whose input is in (row, id) order, then a
 //                         gather and a binary search per row for the CSR offsets.
@@ -21,13 +22,10 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "mdx_common.h"
+#include "mdx_exact.h"
 
 namespace mdx {
 namespace {
-
-typedef float jn_f32x4 __attribute__((ext_vector_type(4)));
-typedef int jn_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int JB_TILES = 8;                     // row tiles (of 16 rows) per block side: 128 rows
 constexpr int JB_ROWS = JB_TILES * 16;
@@ -35,18 +33,11 @@ constexpr int J_GROUP = 16;                     // I blocks that run side by sid
 constexpr double E_Q = 0.5 + 0x1p-15;           // E of the MDX_I8 bound
 constexpr float TINY = 0x1p-149f;               // floor of the factors: inf * factor is never NaN
 
-__device__ __forceinline__ float up_f32(double v)       // the smallest fp32 value >= v (v >= 0); +inf beyond the range
-{
-    float f = (float)v;
-    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
-    return f;
-}
-
 // ---------------------------------------------------------------- per-row factors
 
-__global__ __launch_bounds__(256) void join_stats_kernel(const jn_i32x4 *__restrict__ tiles, const float *__restrict__ scales, int64_t n,
+__global__ __launch_bounds__(256) void join_stats_kernel(const i32x4 *__restrict__ tiles, const float *__restrict__ scales, int64_t n,
                                                          int64_t KB, const float *__restrict__ rows, int64_t ld, int64_t d,
-                                                         jn_f32x4 *__restrict__ stats)
+                                                         f32x4 *__restrict__ stats)
 {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -65,7 +56,7 @@ __global__ __launch_bounds__(256) void join_stats_kernel(const jn_i32x4 *__restr
     const int j = (int)(row & 15);
     uint32_t c1 = 0;
     for (int64_t kb = lane >> 2; kb < KB; kb += 16) {
-        const jn_i32x4 w = tiles[(rt * KB + kb) * 64 + (lane & 3) * 16 + j];
+        const i32x4 w = tiles[(rt * KB + kb) * 64 + (lane & 3) * 16 + j];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int c = (int)(int8_t)(uint8_t)((uint32_t)w[e >> 2] >> (8 * (e & 3)));
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(256) void join_stats_kernel(const jn_i32x4 *__restr
     // a zero row (a == 0) scores exactly 0; any other row needs a scale in [2^-106, 2^40] -- a nonzero row whose scale rounded
     // to 0 (a subnormal max |x|) has scale c = 0 and an error of x itself, which no scale-proportional term covers
     const bool covered = !bad && (a == 0.f || (sc >= 0x1p-106f && sc <= 0x1p40f));
-    jn_f32x4 st;
+    f32x4 st;
     st[0] = sc;
     if (covered) {
         const double ud = (double)d * 0x1p-24, gamma = ud / (1.0 - ud);
@@ -102,7 +93,7 @@ __global__ __launch_bounds__(256) void join_stats_kernel(const jn_i32x4 *__restr
 // ---------------------------------------------------------------- the join kernel
 
 // beta of x in the query role and y in the database role, rounded up (include/mdx.h): b >= beta + 2^-150
-__device__ __forceinline__ float beta_up(jn_f32x4 x, jn_f32x4 y, float c0)
+__device__ __forceinline__ float beta_up(f32x4 x, f32x4 y, float c0)
 {
     const float s = __fadd_rn(__fadd_rn(__fmul_rn(x[1], y[3]), __fmul_rn(y[2], fmaxf(x[0], TINY))), c0);
     return __fmul_rn(s, 1.0f + 0x1p-20f);
@@ -112,20 +103,20 @@ __device__ __forceinline__ float beta_up(jn_f32x4 x, jn_f32x4 y, float c0)
 // rows of B block J; wave (wa, wb) holds its 64 x 64 corner as 4 x 4 MFMA tiles.  16 x 64 tiles of both shards are staged in LDS a
 // 64-k chunk at a time (double buffer, one barrier per chunk).  On entry every wave has left both buffers (a fresh workgroup, or
 // a barrier since the last call); on exit a wave may still read the last buffer.
-__device__ __forceinline__ void block_mma(jn_i32x4 (*lds)[2 * JB_TILES * 64], const jn_i32x4 *__restrict__ a, const jn_i32x4 *__restrict__ b,
-                                          int64_t I, int64_t J, int KB, jn_i32x4 (&acc)[4][4])
+__device__ __forceinline__ void block_mma(i32x4 (*lds)[2 * JB_TILES * 64], const i32x4 *__restrict__ a, const i32x4 *__restrict__ b,
+                                          int64_t I, int64_t J, int KB, i32x4 (&acc)[4][4])
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;                     // the wave's 64 x 64 corner of the block
     // stage loads: thread t moves pieces t, t + 256, t + 512, t + 768 of the 16 tiles (A 0..7, B 8..15) of a chunk
-    const jn_i32x4 *src[4];
+    const i32x4 *src[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int p = tid + 256 * u, t = p >> 6;
         const int64_t rt = t < JB_TILES ? I * JB_TILES + t : J * JB_TILES + (t - JB_TILES);
         src[u] = (t < JB_TILES ? a : b) + rt * KB * 64 + (p & 63);
     }
-    jn_i32x4 reg[4];
+    i32x4 reg[4];
     auto fetch = [&](int kb) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) reg[u] = src[u][(int64_t)kb * 64];
@@ -137,7 +128,7 @@ __device__ __forceinline__ void block_mma(jn_i32x4 (*lds)[2 * JB_TILES * 64], co
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = (jn_i32x4){0, 0, 0, 0};
+        for (int c = 0; c < 4; ++c) acc[r][c] = (i32x4){0, 0, 0, 0};
 
     fetch(0);
     put(0);
@@ -145,8 +136,8 @@ __device__ __forceinline__ void block_mma(jn_i32x4 (*lds)[2 * JB_TILES * 64], co
     for (int kb = 0; kb < KB; ++kb) {
         const bool more = kb + 1 < KB;
         if (more) fetch(kb + 1);                                 // in flight during the MFMAs
-        const jn_i32x4 *s = lds[kb & 1];
-        jn_i32x4 av[4], bv[4];
+        const i32x4 *s = lds[kb & 1];
+        i32x4 av[4], bv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) av[r] = s[(wa * 4 + r) * 64 + lane];
 #pragma unroll
@@ -163,7 +154,7 @@ __device__ __forceinline__ void block_mma(jn_i32x4 (*lds)[2 * JB_TILES * 64], co
 }
 
 // the MDX_I8 score of a pair from its code product and the rounded-up bound b of include/mdx.h (+inf: the pair is not covered)
-__device__ __forceinline__ void pair_bound(int acc, jn_f32x4 xs, jn_f32x4 ys, float c0, float &sc, float &bnd)
+__device__ __forceinline__ void pair_bound(int acc, f32x4 xs, f32x4 ys, float c0, float &sc, float &bnd)
 {
     const float prod = __fmul_rn(ys[0], xs[0]);                              // scale_B * scale_A, as MDX_I8
     sc = __fmul_rn((float)acc, prod);
@@ -175,14 +166,14 @@ __device__ __forceinline__ void pair_bound(int acc, jn_f32x4 xs, jn_f32x4 ys, fl
 // block -- or, symmetric, one group of J_GROUP blocks from I0 against J >= I0.  out: (i << 32 | j) of every candidate, i, j
 // global rows of A and B.  ROWS: the threshold of A row i is taus[i - 128 I0] (any fp32 value: -inf or NaN keeps every pair).
 template <bool SYM, bool ROWS>
-__global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
-                                                      const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
+__global__ __launch_bounds__(256, 2) void join_kernel(const i32x4 *__restrict__ a, const f32x4 *__restrict__ sa, int64_t na,
+                                                      const i32x4 *__restrict__ b, const f32x4 *__restrict__ sb, int64_t nb, int KB,
                                                       int64_t I0, int64_t I1, int64_t NJ, int GS, float tau, const float *__restrict__ taus,
                                                       float c0, uint64_t *__restrict__ out, int64_t capacity,
                                                       unsigned long long *__restrict__ count)
 {
     static_assert(!(SYM && ROWS), "per-row thresholds: the non-symmetric join only");
-    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // [buffer][A tiles, then B tiles][lane]: 2 x 16 KiB
+    __shared__ i32x4 lds[2][2 * JB_TILES * 64];             // [buffer][A tiles, then B tiles][lane]: 2 x 16 KiB
     int64_t I, J;
     const int64_t bid = blockIdx.x;
     if constexpr (SYM) {                                         // J >= I0; I = I0 + (0 .. J_GROUP-1), J >= I
@@ -198,17 +189,17 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wa = wave >> 1, wb = wave & 1;                     // the wave's 64 x 64 corner of the block
 
-    jn_i32x4 acc[4][4];
+    i32x4 acc[4][4];
     block_mma(lds, a, b, I, J, KB, acc);
 
     // Epilogue: lane (g, col) holds rows 4 g .. 4 g + 3 of A tile r against row col of B tile c
     const int g4 = 4 * (lane >> 4), col = lane & 15;
     int64_t jrow[4];
-    jn_f32x4 ys[4];
+    f32x4 ys[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         jrow[c] = (J * JB_TILES + wb * 4 + c) * 16 + col;
-        ys[c] = jrow[c] < nb ? sb[jrow[c]] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+        ys[c] = jrow[c] < nb ? sb[jrow[c]] : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     uint64_t mask = 0;                                           // bit (r * 4 + e) * 4 + c
 #pragma unroll
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void join_kernel(const jn_i32x4 *__restrict
         for (int e = 0; e < 4; ++e) {
             const int64_t irow = (I * JB_TILES + wa * 4 + r) * 16 + g4 + e;
             if (irow >= na) continue;
-            const jn_f32x4 xs = sa[irow];
+            const f32x4 xs = sa[irow];
             const float t = ROWS ? taus[irow - I0 * JB_ROWS] : tau;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -256,7 +247,7 @@ constexpr int KNN_MAX_SLICES = 64;              // one lane per list in knn_sele
 
 // l_ij of include/mdx.h ("exact kNN join"): fl(fl(s - fl(2^-21 |s|)) - b) <= chain_ij, or -inf where the pair gives no lower bound
 // (b infinite, a NaN score, l not finite); -0 is returned as +0, so that equal values are equal bits
-__device__ __forceinline__ float knn_lower(int acc, jn_f32x4 xs, jn_f32x4 ys, float c0)
+__device__ __forceinline__ float knn_lower(int acc, f32x4 xs, f32x4 ys, float c0)
 {
     float sc, bnd;
     pair_bound(acc, xs, ys, c0, sc, bnd);
@@ -270,14 +261,14 @@ __device__ __forceinline__ float knn_lower(int acc, jn_f32x4 xs, jn_f32x4 ys, fl
 // block that overflows the queue (the first ones do) is redone in 16 steps of at most KNN_QCAP values.  Workgroups of one group
 // of GS A blocks and one slice are neighbours in the grid and walk J in the same order (L2 reuse of both operands).
 // lists [S, m, k]: every list sorted descending, -inf beyond the values it holds.
-__global__ __launch_bounds__(256, 2) void knn_bound_kernel(const jn_i32x4 *__restrict__ a, const jn_f32x4 *__restrict__ sa, int64_t na,
-                                                           const jn_i32x4 *__restrict__ b, const jn_f32x4 *__restrict__ sb, int64_t nb, int KB,
+__global__ __launch_bounds__(256, 2) void knn_bound_kernel(const i32x4 *__restrict__ a, const f32x4 *__restrict__ sa, int64_t na,
+                                                           const i32x4 *__restrict__ b, const f32x4 *__restrict__ sb, int64_t nb, int KB,
                                                            int64_t I0, int64_t I1, int64_t NJ, int GS, int S, int k, float c0,
                                                            float *__restrict__ lists, int64_t m)
 {
-    __shared__ jn_i32x4 lds[2][2 * JB_TILES * 64];             // 32 KiB of staging
+    __shared__ i32x4 lds[2][2 * JB_TILES * 64];             // 32 KiB of staging
     __shared__ float top[JB_ROWS * KNN_LD];                      // 32.5 KiB: the k largest of each row
-    __shared__ jn_f32x4 sx[JB_ROWS];                             // the factors of the A rows (zeros beyond the shard)
+    __shared__ f32x4 sx[JB_ROWS];                             // the factors of the A rows (zeros beyond the shard)
     __shared__ float theta[JB_ROWS];
     __shared__ float qval[KNN_QCAP];
     __shared__ uint32_t qrow[KNN_QCAP];
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(256, 2) void knn_bound_kernel(const jn_i32x4 *__res
 
     if (tid < JB_ROWS) {
         theta[tid] = ninf;
-        sx[tid] = I * JB_ROWS + tid < na ? sa[I * JB_ROWS + tid] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+        sx[tid] = I * JB_ROWS + tid < na ? sa[I * JB_ROWS + tid] : (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     if (tid < 2) qn[tid] = 0;
     int cnt = 0, amin = 0;                                       // of thread tid < 128: its list's length and the slot of its minimum
@@ -331,15 +322,15 @@ __global__ __launch_bounds__(256, 2) void knn_bound_kernel(const jn_i32x4 *__res
     int ph = 0;
     const int64_t j_lo = sl * NJ / S, j_hi = (sl + 1) * NJ / S;
     for (int64_t J = j_lo; J < j_hi; ++J) {
-        jn_i32x4 acc[4][4];
+        i32x4 acc[4][4];
         block_mma(lds, a, b, I, J, KB, acc);
 
         int64_t jrow[4];
-        jn_f32x4 ys[4];
+        f32x4 ys[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             jrow[c] = (J * JB_TILES + wb * 4 + c) * 16 + col;
-            ys[c] = jrow[c] < nb ? sb[jrow[c]] : (jn_f32x4){0.f, 0.f, 0.f, 0.f};
+            ys[c] = jrow[c] < nb ? sb[jrow[c]] : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         uint64_t mask = 0;                                       // bit (r * 4 + e) * 4 + c: l above the row's theta as it was
 #pragma unroll
@@ -349,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void knn_bound_kernel(const jn_i32x4 *__res
                 const int row = (wa * 4 + r) * 16 + g4 + e;
                 if (I * JB_ROWS + row >= na) continue;
                 const float t = theta[row];
-                const jn_f32x4 xs = sx[row];
+                const f32x4 xs = sx[row];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     if (jrow[c] >= nb) continue;
@@ -449,17 +440,6 @@ constexpr int EX_TC = 64;              // candidates per workgroup: one per lane
 constexpr int EX_KC = 128;             // k per stage
 constexpr int EX_LD = EX_KC + 4;
 
-__device__ __forceinline__ jn_f32x4 piece(const float *rows, int64_t id, int64_t ld, int64_t d, int64_t k, bool vec)
-{
-    jn_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (id < 0) return v;
-    const float *p = rows + id * ld;
-    if (vec && k + 4 <= d) return *(const jn_f32x4 *)(p + k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = k + e < d ? p[k + e] : 0.f;
-    return v;
-}
-
 // sorted candidates (i << 32 | j) -> key (i - m_lo) << 32 | desc_key(chain) for a hit, ~0 otherwise; idx = position.  ALL (the kNN
 // join): no threshold, every candidate is kept, a NaN chain too (desc_key ranks it last in its row)
 template <bool ALL>
@@ -480,22 +460,21 @@ __global__ __launch_bounds__(256) void exact_kernel(const float *__restrict__ ra
         ia[u] = p < P ? (int64_t)(kk >> 32) : -1;
         ib[u] = p < P ? (int64_t)(kk & 0xFFFFFFFFu) : -1;
     }
-    const int64_t d_pad = (d + 63) / 64 * 64;
-    const int64_t stages = (d_pad + EX_KC - 1) / EX_KC;
-    jn_f32x4 ra_[8], rb_[8];
+    const int64_t d_pad = chain_pad(d), stages = chain_stages(d_pad, EX_KC);
+    f32x4 ra_[8], rb_[8];
     auto fetch = [&](int64_t k0) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            ra_[u] = piece(ra, ia[u], lda, d, k0 + 4 * l32, vec);
-            rb_[u] = piece(rb, ib[u], ldb, d, k0 + 4 * l32, vec);
+            ra_[u] = row_piece(ra, ia[u], lda, d, k0 + 4 * l32, vec);
+            rb_[u] = row_piece(rb, ib[u], ldb, d, k0 + 4 * l32, vec);
         }
     };
     auto put = [&]() {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int c = wave * 16 + 2 * u + half;
-            *(jn_f32x4 *)(ta + c * EX_LD + 4 * l32) = ra_[u];
-            *(jn_f32x4 *)(tb + c * EX_LD + 4 * l32) = rb_[u];
+            *(f32x4 *)(ta + c * EX_LD + 4 * l32) = ra_[u];
+            *(f32x4 *)(tb + c * EX_LD + 4 * l32) = rb_[u];
         }
     };
     float acc = 0.f;
@@ -506,15 +485,12 @@ __global__ __launch_bounds__(256) void exact_kernel(const float *__restrict__ ra
         const int64_t k0 = s * EX_KC;
         if (s + 1 < stages) fetch(k0 + EX_KC);
         if (wave == 0) {
-            const int kend = (int)(d_pad - k0 < EX_KC ? d_pad - k0 : EX_KC);     // a multiple of 64
+            const int kend = chain_kend(d_pad, k0, EX_KC);
             const float *x = ta + lane * EX_LD, *y = tb + lane * EX_LD;
             for (int kk = 0; kk < kend; kk += 4) {
-                const jn_f32x4 xv = *(const jn_f32x4 *)(x + kk);
-                const jn_f32x4 yv = *(const jn_f32x4 *)(y + kk);
-                acc = __builtin_fmaf(xv[0], yv[0], acc);
-                acc = __builtin_fmaf(xv[1], yv[1], acc);
-                acc = __builtin_fmaf(xv[2], yv[2], acc);
-                acc = __builtin_fmaf(xv[3], yv[3], acc);
+                const f32x4 xv = *(const f32x4 *)(x + kk);
+                const f32x4 yv = *(const f32x4 *)(y + kk);
+                acc = chain_step4(acc, xv, yv);
             }
         }
         if (s + 1 < stages) {
@@ -689,36 +665,51 @@ size_t scan_bytes(int64_t m)
     return t;
 }
 
-int64_t resolve_layout(int64_t P, int64_t m, Carve &cv, uint64_t **cs, float **score, uint64_t **key, int32_t **idx, uint64_t **key2,
-                       int32_t **idx2, void **tmp, size_t *tmp_bytes)
+// the workspace of the two resolves: the sorted candidates, their chains, the (key, idx) pairs before and after the sort, and
+// `extra` int64 words behind them (the kNN join's offsets; none for extra == 0)
+struct ResolveWs {
+    uint64_t *cs, *key, *key2;
+    float *score;
+    int32_t *idx, *idx2;
+    void *tmp;
+    size_t tmp_bytes;
+    int64_t *offsets;
+};
+
+void resolve_layout(int64_t P, int64_t m, int64_t extra, Carve &cv, ResolveWs &w)
 {
-    *cs = cv.take<uint64_t>(P);
-    *score = cv.take<float>(P);
-    *key = cv.take<uint64_t>(P);
-    *idx = cv.take<int32_t>(P);
-    *key2 = cv.take<uint64_t>(P);
-    *idx2 = cv.take<int32_t>(P);
-    const size_t t = std::max(sort_bytes(P, key_bits(m)), cand_sort_bytes(P, 64));
-    *tmp_bytes = t;
-    *tmp = cv.take<char>((int64_t)t);
-    return cv.used;
+    w.cs = cv.take<uint64_t>(P);
+    w.score = cv.take<float>(P);
+    w.key = cv.take<uint64_t>(P);
+    w.idx = cv.take<int32_t>(P);
+    w.key2 = cv.take<uint64_t>(P);
+    w.idx2 = cv.take<int32_t>(P);
+    w.tmp_bytes = std::max(sort_bytes(P, key_bits(m)), cand_sort_bytes(P, 64));
+    w.tmp = cv.take<char>((int64_t)w.tmp_bytes);
+    w.offsets = extra ? cv.take<int64_t>(extra) : nullptr;
 }
 
-int64_t select_layout(int64_t m, int64_t capacity, Carve &cv, int64_t **counts, uint64_t **key, int32_t **idx, uint64_t **key2,
-                      int32_t **idx2, int64_t **ids, float **vals, void **tmp, size_t *tmp_bytes)
+struct SelectWs {
+    int64_t *counts, *ids;
+    uint64_t *key, *key2;
+    int32_t *idx, *idx2;
+    float *vals;
+    void *tmp;
+    size_t tmp_bytes;
+};
+
+void select_layout(int64_t m, int64_t capacity, Carve &cv, SelectWs &w)
 {
     const int64_t P = capacity > 0 ? capacity : 1;
-    *counts = cv.take<int64_t>(m + 1);
-    *key = cv.take<uint64_t>(P);
-    *idx = cv.take<int32_t>(P);
-    *key2 = cv.take<uint64_t>(P);
-    *idx2 = cv.take<int32_t>(P);
-    *ids = cv.take<int64_t>(P);
-    *vals = cv.take<float>(P);
-    const size_t t = std::max(sort_bytes(P, key_bits(m)), scan_bytes(m));
-    *tmp_bytes = t;
-    *tmp = cv.take<char>((int64_t)t);
-    return cv.used;
+    w.counts = cv.take<int64_t>(m + 1);
+    w.key = cv.take<uint64_t>(P);
+    w.idx = cv.take<int32_t>(P);
+    w.key2 = cv.take<uint64_t>(P);
+    w.idx2 = cv.take<int32_t>(P);
+    w.ids = cv.take<int64_t>(P);
+    w.vals = cv.take<float>(P);
+    w.tmp_bytes = std::max(sort_bytes(P, key_bits(m)), scan_bytes(m));
+    w.tmp = cv.take<char>((int64_t)w.tmp_bytes);
 }
 
 constexpr int64_t J_MAX_ITEMS = (1ll << 31) - 1;     // hipcub item counts and the int32 positions of the sort
@@ -732,6 +723,88 @@ __global__ __launch_bounds__(256) void center_kernel(const float *__restrict__ s
         const float x = layout == MDX_ROW_MAJOR ? src[e] : src[k * n + row];
         out[e] = center ? x - center[k] : x;
     }
+}
+
+// the shards, sizes and launch geometry that the candidate and bound sweeps share
+struct JoinArgs {
+    const void *ta, *tb;
+    int64_t na, nb, d, I0, I1, NJ, gs, blocks;
+    int KB;
+    float c0;
+};
+
+int join_args(const char *who, const mdx_index *a, const mdx_index *b, int64_t a_lo, int64_t a_hi, JoinArgs *g)
+{
+    const float *sca = nullptr, *scb = nullptr;
+    int64_t rta = 0, kba = 0, rtb = 0, kbb = 0, db = 0;
+    MDX_CHECK_ARG(i8_view(a, &g->ta, &sca, &g->na, &rta, &kba) && i8_view(b, &g->tb, &scb, &g->nb, &rtb, &kbb),
+                  "%s: int8 shards are needed (an fp16 or fp32 one has no bound)", who);
+    (void)mdx_index_info(a, nullptr, &g->d, nullptr, nullptr);
+    (void)mdx_index_info(b, nullptr, &db, nullptr, nullptr);
+    MDX_CHECK_ARG(g->d == db, "%s: dimensions %lld and %lld differ", who, (long long)g->d, (long long)db);
+    MDX_CHECK_ARG(g->na < (1ll << 31) && g->nb < (1ll << 31), "%s: n >= 2^31", who);
+    MDX_CHECK_ARG(a_lo >= 0 && a_lo < a_hi && a_hi <= g->na && a_lo % JB_ROWS == 0,
+                  "%s: rows [%lld, %lld) of A: 0 <= lo < hi <= n=%lld and lo a multiple of %d", who, (long long)a_lo, (long long)a_hi,
+                  (long long)g->na, JB_ROWS);
+    g->I0 = a_lo / JB_ROWS;
+    g->I1 = ceil_div(a_hi, (int64_t)JB_ROWS);
+    g->NJ = ceil_div(g->nb, (int64_t)JB_ROWS);
+    g->KB = (int)kba;
+    g->c0 = (float)((double)(g->d + 2) * 0x1p-149);             // exact: a multiple of 2^-149 below 2^-126
+    return MDX_OK;
+}
+
+// the grid of a non-symmetric sweep: the A blocks in groups of g->gs (<= J_GROUP) side by side, `per` workgroups (J blocks or
+// slices) for each
+int sweep_grid(const char *who, JoinArgs *g, int64_t per)
+{
+    g->gs = std::min(g->I1 - g->I0, (int64_t)J_GROUP);          // a range search of <= 128 queries is one block row
+    g->blocks = ceil_div(g->I1 - g->I0, g->gs) * g->gs * per;
+    MDX_CHECK_ARG(g->blocks < (1ll << 31), "%s: too many blocks for one launch", who);
+    return MDX_OK;
+}
+
+// bytes of the resolve layout for P candidates of m rows with `extra` words behind it (0: the size is not defined)
+int64_t resolve_bytes(int64_t P, int64_t m, int64_t extra)
+{
+    if (P < 1 || m < 1 || P > J_MAX_ITEMS || m > J_MAX_ITEMS) return 0;
+    Carve cv{nullptr};
+    ResolveWs w;
+    resolve_layout(P, m, extra, cv, w);
+    return cv.used + 256;
+}
+
+// What mdx_join_resolve and mdx_knn_resolve share, in the name `who` of the entry point: the checks of the operands and of the
+// workspace, the carve (with `extra` words, as who's size function counts them), the candidates in (i, j) order (the chains then
+// run row-grouped, and the stable sort breaks ties by ascending j), their chains (all: no threshold, every candidate is kept)
+// and the stable (row, desc_key) sort.  It leaves the sorted keys and positions in w.key2 / w.idx2.
+// The callers check their pointers and their own argument (k, tau) first, so among several invalid arguments that one is
+// reported before P, m, d, lda / ldb and m_lo; when each entry point carried its own copy of these checks, k came after the
+// two checks of P and m and tau came last.  The status is MDX_ERR_INVALID either way.
+int resolve_front(const char *who, const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs,
+                  int64_t P, float tau, bool all, int64_t m_lo, int64_t m, int64_t extra, void *workspace, int64_t workspace_bytes,
+                  hipStream_t s, ResolveWs &w)
+{
+    MDX_CHECK_ARG(P >= 1 && m >= 1 && d >= 1, "%s: P=%lld m=%lld d=%lld must be >= 1", who, (long long)P, (long long)m, (long long)d);
+    MDX_CHECK_ARG(P <= J_MAX_ITEMS && m <= J_MAX_ITEMS, "%s: P=%lld or m=%lld >= 2^31", who, (long long)P, (long long)m);
+    MDX_CHECK_ARG(lda >= d && ldb >= d, "%s: lda=%lld / ldb=%lld < d=%lld", who, (long long)lda, (long long)ldb, (long long)d);
+    MDX_CHECK_ARG(m_lo >= 0, "%s: m_lo=%lld < 0", who, (long long)m_lo);
+    const int64_t need = resolve_bytes(P, m, extra);
+    MDX_CHECK_WORKSPACE(who, workspace, workspace_bytes, need);
+    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};     // the + 256 of the size covers the alignment
+    resolve_layout(P, m, extra, cv, w);
+    MDX_HIP(hipcub::DeviceRadixSort::SortKeys(w.tmp, w.tmp_bytes, pairs, w.cs, (int)P, 0, 64, s));
+    const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
+    const dim3 grid((unsigned)ceil_div(P, (int64_t)EX_TC));
+    if (all)
+        hipLaunchKernelGGL(exact_kernel<true>, grid, dim3(256), 0, s, rows_a, lda, rows_b, ldb, d, (const uint64_t *)w.cs, P, 0.f, m_lo, vec,
+                           w.score, w.key, w.idx);
+    else
+        hipLaunchKernelGGL(exact_kernel<false>, grid, dim3(256), 0, s, rows_a, lda, rows_b, ldb, d, (const uint64_t *)w.cs, P, tau, m_lo, vec,
+                           w.score, w.key, w.idx);
+    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(w.tmp, w.tmp_bytes, (const uint64_t *)w.key, w.key2, (const int32_t *)w.idx, w.idx2, (int)P, 0,
+                                               key_bits(m), s));
+    return MDX_OK;
 }
 
 }  // namespace
@@ -763,8 +836,8 @@ int mdx_join_stats(const mdx_index *index, const float *rows, int64_t ld, float 
     MDX_CHECK_ARG(mdx_index_info(index, nullptr, &d, nullptr, nullptr) == MDX_OK, "mdx_join_stats: index info");
     MDX_CHECK_ARG(ld >= d, "mdx_join_stats: ld=%lld < d=%lld", (long long)ld, (long long)d);
     MDX_CHECK_ARG(ceil_div(n, (int64_t)4) < (1ll << 31), "mdx_join_stats: shard too large for one launch");
-    hipLaunchKernelGGL(join_stats_kernel, dim3((unsigned)ceil_div(n, (int64_t)4)), dim3(256), 0, (hipStream_t)stream, (const jn_i32x4 *)tiles,
-                       scales, n, KB, rows, ld, d, (jn_f32x4 *)stats);
+    hipLaunchKernelGGL(join_stats_kernel, dim3((unsigned)ceil_div(n, (int64_t)4)), dim3(256), 0, (hipStream_t)stream, (const i32x4 *)tiles,
+                       scales, n, KB, rows, ld, d, (f32x4 *)stats);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }
@@ -777,68 +850,25 @@ int mdx_join_candidates(const mdx_index *a, const float *stats_a, const mdx_inde
     MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_join_candidates: tau must be finite");
     MDX_CHECK_ARG(capacity >= 0, "mdx_join_candidates: capacity=%lld < 0", (long long)capacity);
     MDX_CHECK_ARG(!symmetric || a == b, "mdx_join_candidates: the self-join needs a == b");
-    const void *ta = nullptr, *tb = nullptr;
-    const float *sca = nullptr, *scb = nullptr;
-    int64_t na = 0, rta = 0, kba = 0, nb = 0, rtb = 0, kbb = 0, da = 0, db = 0;
-    MDX_CHECK_ARG(i8_view(a, &ta, &sca, &na, &rta, &kba) && i8_view(b, &tb, &scb, &nb, &rtb, &kbb),
-                  "mdx_join_candidates: int8 shards are needed (an fp16 or fp32 one has no bound)");
-    (void)mdx_index_info(a, nullptr, &da, nullptr, nullptr);
-    (void)mdx_index_info(b, nullptr, &db, nullptr, nullptr);
-    MDX_CHECK_ARG(da == db, "mdx_join_candidates: dimensions %lld and %lld differ", (long long)da, (long long)db);
-    MDX_CHECK_ARG(na < (1ll << 31) && nb < (1ll << 31), "mdx_join_candidates: n >= 2^31");
-    MDX_CHECK_ARG(a_lo >= 0 && a_lo < a_hi && a_hi <= na && a_lo % JB_ROWS == 0,
-                  "mdx_join_candidates: rows [%lld, %lld) of A: 0 <= lo < hi <= n=%lld and lo a multiple of %d", (long long)a_lo, (long long)a_hi,
-                  (long long)na, JB_ROWS);
+    JoinArgs g;
+    if (const int rc = join_args("mdx_join_candidates", a, b, a_lo, a_hi, &g)) return rc;
     hipStream_t s = (hipStream_t)stream;
     MDX_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
-    const int64_t I0 = a_lo / JB_ROWS, I1 = ceil_div(a_hi, (int64_t)JB_ROWS), NJ = ceil_div(nb, (int64_t)JB_ROWS);
-    const float c0 = (float)((double)(da + 2) * 0x1p-149);      // exact: a multiple of 2^-149 below 2^-126
     if (symmetric) {
-        for (int64_t g = I0; g < I1; g += J_GROUP) {             // one launch per group of J_GROUP I blocks: J >= g only
-            const int64_t blocks = J_GROUP * (NJ - g);
+        for (int64_t i = g.I0; i < g.I1; i += J_GROUP) {         // one launch per group of J_GROUP I blocks: J >= i only
+            const int64_t blocks = J_GROUP * (g.NJ - i);
             MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
-            hipLaunchKernelGGL((join_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
-                               (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, g, std::min(g + J_GROUP, I1), NJ, J_GROUP, tau,
-                               (const float *)nullptr, c0, pairs, capacity, (unsigned long long *)count);
+            hipLaunchKernelGGL((join_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, (const i32x4 *)g.ta, (const f32x4 *)stats_a, a_hi,
+                               (const i32x4 *)g.tb, (const f32x4 *)stats_b, g.nb, g.KB, i, std::min(i + J_GROUP, g.I1), g.NJ, J_GROUP, tau,
+                               (const float *)nullptr, g.c0, pairs, capacity, (unsigned long long *)count);
         }
     } else {
-        const int64_t gs = std::min(I1 - I0, (int64_t)J_GROUP);    // a range search of <= 128 queries is one block row
-        const int64_t blocks = ceil_div(I1 - I0, gs) * gs * NJ;
-        MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates: too many blocks for one launch");
-        hipLaunchKernelGGL((join_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)ta, (const jn_f32x4 *)stats_a, a_hi,
-                           (const jn_i32x4 *)tb, (const jn_f32x4 *)stats_b, nb, (int)kba, I0, I1, NJ, (int)gs, tau, (const float *)nullptr, c0, pairs,
-                           capacity, (unsigned long long *)count);
+        if (const int rc = sweep_grid("mdx_join_candidates", &g, g.NJ)) return rc;
+        hipLaunchKernelGGL((join_kernel<false, false>), dim3((unsigned)g.blocks), dim3(256), 0, s, (const i32x4 *)g.ta, (const f32x4 *)stats_a, a_hi,
+                           (const i32x4 *)g.tb, (const f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)g.gs, tau, (const float *)nullptr, g.c0,
+                           pairs, capacity, (unsigned long long *)count);
     }
     MDX_LAUNCH_CHECK();
-    return MDX_OK;
-}
-
-// the shards, sizes and launch geometry that mdx_knn_bounds and mdx_join_candidates_rows share
-struct JoinArgs {
-    const void *ta, *tb;
-    int64_t na, nb, d, I0, I1, NJ;
-    int KB;
-    float c0;
-};
-
-int join_args(const char *who, const mdx_index *a, const mdx_index *b, int64_t a_lo, int64_t a_hi, JoinArgs *g)
-{
-    const float *sca = nullptr, *scb = nullptr;
-    int64_t rta = 0, kba = 0, rtb = 0, kbb = 0, db = 0;
-    MDX_CHECK_ARG(i8_view(a, &g->ta, &sca, &g->na, &rta, &kba) && i8_view(b, &g->tb, &scb, &g->nb, &rtb, &kbb),
-                  "%s: int8 shards are needed (an fp16 or fp32 one has no bound)", who);
-    (void)mdx_index_info(a, nullptr, &g->d, nullptr, nullptr);
-    (void)mdx_index_info(b, nullptr, &db, nullptr, nullptr);
-    MDX_CHECK_ARG(g->d == db, "%s: dimensions %lld and %lld differ", who, (long long)g->d, (long long)db);
-    MDX_CHECK_ARG(g->na < (1ll << 31) && g->nb < (1ll << 31), "%s: n >= 2^31", who);
-    MDX_CHECK_ARG(a_lo >= 0 && a_lo < a_hi && a_hi <= g->na && a_lo % JB_ROWS == 0,
-                  "%s: rows [%lld, %lld) of A: 0 <= lo < hi <= n=%lld and lo a multiple of %d", who, (long long)a_lo, (long long)a_hi,
-                  (long long)g->na, JB_ROWS);
-    g->I0 = a_lo / JB_ROWS;
-    g->I1 = ceil_div(a_hi, (int64_t)JB_ROWS);
-    g->NJ = ceil_div(g->nb, (int64_t)JB_ROWS);
-    g->KB = (int)kba;
-    g->c0 = (float)((double)(g->d + 2) * 0x1p-149);             // exact: a multiple of 2^-149 below 2^-126
     return MDX_OK;
 }
 
@@ -881,18 +911,12 @@ int mdx_knn_bounds(const mdx_index *a, const float *stats_a, const mdx_index *b,
     if (const int rc = join_args("mdx_knn_bounds", a, b, a_lo, a_hi, &g)) return rc;
     MDX_CHECK_ARG(k <= g.nb, "mdx_knn_bounds: k=%lld > the %lld rows of B", (long long)k, (long long)g.nb);
     const int64_t m = a_hi - a_lo, need = mdx_knn_bounds_workspace(m, k, g.nb, slices);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_knn_bounds: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_bounds");
+    MDX_CHECK_WORKSPACE("mdx_knn_bounds", workspace, workspace_bytes, need);
     const int S = knn_slices(m, g.nb, slices);
-    const int64_t gs = std::min(g.I1 - g.I0, (int64_t)J_GROUP);
-    const int64_t blocks = ceil_div(g.I1 - g.I0, gs) * gs * S;
-    MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_knn_bounds: too many blocks for one launch");
+    if (const int rc = sweep_grid("mdx_knn_bounds", &g, S)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(knn_bound_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)g.ta, (const jn_f32x4 *)stats_a, a_hi,
-                       (const jn_i32x4 *)g.tb, (const jn_f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)gs, S, (int)k, g.c0,
+    hipLaunchKernelGGL(knn_bound_kernel, dim3((unsigned)g.blocks), dim3(256), 0, s, (const i32x4 *)g.ta, (const f32x4 *)stats_a, a_hi,
+                       (const i32x4 *)g.tb, (const f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)g.gs, S, (int)k, g.c0,
                        (float *)workspace, m);
     hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)ceil_div(m, (int64_t)4)), dim3(256), 0, s, (const float *)workspace, m, S, (int)k, t);
     MDX_LAUNCH_CHECK();
@@ -907,116 +931,53 @@ int mdx_join_candidates_rows(const mdx_index *a, const float *stats_a, const mdx
     MDX_CHECK_ARG(capacity >= 0, "mdx_join_candidates_rows: capacity=%lld < 0", (long long)capacity);
     JoinArgs g;
     if (const int rc = join_args("mdx_join_candidates_rows", a, b, a_lo, a_hi, &g)) return rc;
-    const int64_t gs = std::min(g.I1 - g.I0, (int64_t)J_GROUP);
-    const int64_t blocks = ceil_div(g.I1 - g.I0, gs) * gs * g.NJ;
-    MDX_CHECK_ARG(blocks < (1ll << 31), "mdx_join_candidates_rows: too many blocks for one launch");
+    if (const int rc = sweep_grid("mdx_join_candidates_rows", &g, g.NJ)) return rc;
     hipStream_t s = (hipStream_t)stream;
     MDX_HIP(hipMemsetAsync(count, 0, sizeof(int64_t), s));
-    hipLaunchKernelGGL((join_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, (const jn_i32x4 *)g.ta, (const jn_f32x4 *)stats_a, a_hi,
-                       (const jn_i32x4 *)g.tb, (const jn_f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)gs, 0.f, tau, g.c0, pairs, capacity,
+    hipLaunchKernelGGL((join_kernel<false, true>), dim3((unsigned)g.blocks), dim3(256), 0, s, (const i32x4 *)g.ta, (const f32x4 *)stats_a, a_hi,
+                       (const i32x4 *)g.tb, (const f32x4 *)stats_b, g.nb, g.KB, g.I0, g.I1, g.NJ, (int)g.gs, 0.f, tau, g.c0, pairs, capacity,
                        (unsigned long long *)count);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }
 
-int64_t mdx_knn_resolve_workspace(int64_t P, int64_t m)
-{
-    if (P < 1 || m < 1 || P > J_MAX_ITEMS || m > J_MAX_ITEMS) return 0;
-    Carve cv{nullptr};
-    uint64_t *cs, *key, *key2;
-    int32_t *idx, *idx2;
-    float *score;
-    void *tmp;
-    size_t tb;
-    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
-    cv.take<int64_t>(m + 1);
-    return cv.used + 256;
-}
+int64_t mdx_knn_resolve_workspace(int64_t P, int64_t m) { return resolve_bytes(P, m, m + 1); }     // the offsets on top
 
 int mdx_knn_resolve(const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs, int64_t P,
                     int64_t m_lo, int64_t m, int64_t k, int64_t *ids, float *scores, int32_t *counts, void *workspace, int64_t workspace_bytes,
                     void *stream)
 {
     MDX_CHECK_ARG(rows_a && rows_b && pairs && ids && scores && counts, "mdx_knn_resolve: NULL pointer");
-    MDX_CHECK_ARG(P >= 1 && m >= 1 && d >= 1, "mdx_knn_resolve: P=%lld m=%lld d=%lld must be >= 1", (long long)P, (long long)m, (long long)d);
-    MDX_CHECK_ARG(P <= J_MAX_ITEMS && m <= J_MAX_ITEMS, "mdx_knn_resolve: P=%lld or m=%lld >= 2^31", (long long)P, (long long)m);
     MDX_CHECK_ARG(k >= 1 && k <= KNN_MAX_K, "mdx_knn_resolve: k=%lld must be in [1, MDX_KNN_JOIN_MAX_K = %d]", (long long)k, KNN_MAX_K);
-    MDX_CHECK_ARG(lda >= d && ldb >= d, "mdx_knn_resolve: lda=%lld / ldb=%lld < d=%lld", (long long)lda, (long long)ldb, (long long)d);
-    MDX_CHECK_ARG(m_lo >= 0, "mdx_knn_resolve: m_lo=%lld < 0", (long long)m_lo);
-    const int64_t need = mdx_knn_resolve_workspace(P, m);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_knn_resolve: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_knn_resolve");
-    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};
-    uint64_t *cs, *key, *key2;
-    int32_t *idx, *idx2;
-    float *score;
-    void *tmp;
-    size_t tb;
-    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
-    int64_t *offsets = cv.take<int64_t>(m + 1);
     hipStream_t s = (hipStream_t)stream;
-    // as mdx_join_resolve, with no threshold: (i, j) order, the chains, the stable (row, desc_key) sort, then the first k per row
-    MDX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tb, pairs, cs, (int)P, 0, 64, s));
-    const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
-    hipLaunchKernelGGL(exact_kernel<true>, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
-                       (const uint64_t *)cs, P, 0.f, m_lo, vec, score, key, idx);
-    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
-    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, P, m, offsets);
-    hipLaunchKernelGGL(knn_dense_kernel, dim3((unsigned)ceil_div(m * k, (int64_t)256)), dim3(256), 0, s, (const int32_t *)idx2,
-                       (const uint64_t *)cs, (const float *)score, (const int64_t *)offsets, m, k, ids, scores, counts);
+    ResolveWs w;
+    if (const int rc = resolve_front("mdx_knn_resolve", rows_a, lda, rows_b, ldb, d, pairs, P, 0.f, true, m_lo, m, m + 1, workspace,
+                                     workspace_bytes, s, w))
+        return rc;
+    // the CSR of the sorted candidates, then the first k of every row
+    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)w.key2, P, m, w.offsets);
+    hipLaunchKernelGGL(knn_dense_kernel, dim3((unsigned)ceil_div(m * k, (int64_t)256)), dim3(256), 0, s, (const int32_t *)w.idx2,
+                       (const uint64_t *)w.cs, (const float *)w.score, (const int64_t *)w.offsets, m, k, ids, scores, counts);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }
 
-int64_t mdx_join_resolve_workspace(int64_t P, int64_t m)
-{
-    if (P < 1 || m < 1 || P > J_MAX_ITEMS || m > J_MAX_ITEMS) return 0;
-    Carve cv{nullptr};
-    uint64_t *cs, *key, *key2;
-    int32_t *idx, *idx2;
-    float *score;
-    void *tmp;
-    size_t tb;
-    return resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb) + 256;
-}
+int64_t mdx_join_resolve_workspace(int64_t P, int64_t m) { return resolve_bytes(P, m, 0); }
 
 int mdx_join_resolve(const float *rows_a, int64_t lda, const float *rows_b, int64_t ldb, int64_t d, const uint64_t *pairs, int64_t P,
                      float tau, int64_t m_lo, int64_t m, int64_t *offsets, int64_t *ids, float *scores, void *workspace, int64_t workspace_bytes,
                      void *stream)
 {
     MDX_CHECK_ARG(rows_a && rows_b && pairs && offsets && ids && scores, "mdx_join_resolve: NULL pointer");
-    MDX_CHECK_ARG(P >= 1 && m >= 1 && d >= 1, "mdx_join_resolve: P=%lld m=%lld d=%lld must be >= 1", (long long)P, (long long)m, (long long)d);
-    MDX_CHECK_ARG(P <= J_MAX_ITEMS && m <= J_MAX_ITEMS, "mdx_join_resolve: P=%lld or m=%lld >= 2^31", (long long)P, (long long)m);
-    MDX_CHECK_ARG(lda >= d && ldb >= d, "mdx_join_resolve: lda=%lld / ldb=%lld < d=%lld", (long long)lda, (long long)ldb, (long long)d);
-    MDX_CHECK_ARG(m_lo >= 0, "mdx_join_resolve: m_lo=%lld < 0", (long long)m_lo);
     MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_join_resolve: tau must be finite");
-    const int64_t need = mdx_join_resolve_workspace(P, m);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_join_resolve: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_join_resolve");
-    Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};     // the + 256 of the size covers the alignment
-    uint64_t *cs, *key, *key2;
-    int32_t *idx, *idx2;
-    float *score;
-    void *tmp;
-    size_t tb;
-    resolve_layout(P, m, cv, &cs, &score, &key, &idx, &key2, &idx2, &tmp, &tb);
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)ceil_div(P, (int64_t)256);
-    // candidates in (i, j) order: the chains then run row-grouped, and the stable sort below breaks ties by ascending j
-    MDX_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tb, pairs, cs, (int)P, 0, 64, s));
-    const bool vec = lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)rows_a & 15) == 0 && ((uintptr_t)rows_b & 15) == 0;
-    hipLaunchKernelGGL(exact_kernel<false>, dim3((unsigned)ceil_div(P, (int64_t)EX_TC)), dim3(256), 0, s, rows_a, lda, rows_b, ldb, d,
-                       (const uint64_t *)cs, P, tau, m_lo, vec, score, key, idx);
-    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
-    hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(256), 0, s, (const uint64_t *)key2, (const int32_t *)idx2, P, (const uint64_t *)cs,
-                       (const int64_t *)nullptr, (const float *)score, ids, scores);
-    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, P, m, offsets);
+    ResolveWs w;
+    if (const int rc = resolve_front("mdx_join_resolve", rows_a, lda, rows_b, ldb, d, pairs, P, tau, false, m_lo, m, 0, workspace,
+                                     workspace_bytes, s, w))
+        return rc;
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)w.key2, (const int32_t *)w.idx2,
+                       P, (const uint64_t *)w.cs, (const int64_t *)nullptr, (const float *)w.score, ids, scores);
+    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)ceil_div(m + 1, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)w.key2, P, m, offsets);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }
@@ -1025,13 +986,9 @@ int64_t mdx_range_select_workspace(int64_t m, int64_t capacity)
 {
     if (m < 1 || capacity < 0 || m > J_MAX_ITEMS || capacity > J_MAX_ITEMS) return 0;
     Carve cv{nullptr};
-    int64_t *counts, *ids;
-    uint64_t *key, *key2;
-    int32_t *idx, *idx2;
-    float *vals;
-    void *tmp;
-    size_t tb;
-    return select_layout(m, capacity, cv, &counts, &key, &idx, &key2, &idx2, &ids, &vals, &tmp, &tb) + 256;
+    SelectWs w;
+    select_layout(m, capacity, cv, w);
+    return cv.used + 256;
 }
 
 int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, float tau, int64_t diag, int64_t *offsets, int64_t *ids,
@@ -1045,30 +1002,22 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
     MDX_CHECK_ARG(capacity >= 0, "mdx_range_select: capacity=%lld < 0", (long long)capacity);
     MDX_CHECK_ARG(__builtin_isfinite(tau), "mdx_range_select: tau must be finite");
     const int64_t need = mdx_range_select_workspace(m, capacity);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_range_select: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_range_select");
+    MDX_CHECK_WORKSPACE("mdx_range_select", workspace, workspace_bytes, need);
     Carve cv{(char *)round_up((int64_t)(uintptr_t)workspace, 256)};
-    int64_t *counts, *hid;
-    uint64_t *key, *key2;
-    int32_t *idx, *idx2;
-    float *vals;
-    void *tmp;
-    size_t tb;
-    select_layout(m, capacity, cv, &counts, &key, &idx, &key2, &idx2, &hid, &vals, &tmp, &tb);
+    SelectWs w;
+    select_layout(m, capacity, cv, w);
     const int64_t P = capacity > 0 ? capacity : 1;
     hipStream_t s = (hipStream_t)stream;
-    MDX_HIP(hipMemsetAsync(counts + m, 0, sizeof(int64_t), s));
-    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)m), dim3(256), 0, s, scores, n, ld, diag, tau, counts);
-    MDX_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, (const int64_t *)counts, offsets, (int)(m + 1), s));
-    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, key, idx, P);
+    MDX_HIP(hipMemsetAsync(w.counts + m, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL(select_count_kernel, dim3((unsigned)m), dim3(256), 0, s, scores, n, ld, diag, tau, w.counts);
+    MDX_HIP(hipcub::DeviceScan::ExclusiveSum(w.tmp, w.tmp_bytes, (const int64_t *)w.counts, offsets, (int)(m + 1), s));
+    hipLaunchKernelGGL(fill_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, w.key, w.idx, P);
     hipLaunchKernelGGL(select_write_kernel, dim3((unsigned)m), dim3(256), 0, s, scores, n, ld, diag, tau, (const int64_t *)offsets, m, capacity,
-                       key, idx, hid, vals);
-    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, (const uint64_t *)key, key2, (const int32_t *)idx, idx2, (int)P, 0, key_bits(m), s));
-    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)key2, (const int32_t *)idx2, P,
-                       (const uint64_t *)nullptr, (const int64_t *)hid, (const float *)vals, ids, out_scores);
+                       w.key, w.idx, w.ids, w.vals);
+    MDX_HIP(hipcub::DeviceRadixSort::SortPairs(w.tmp, w.tmp_bytes, (const uint64_t *)w.key, w.key2, (const int32_t *)w.idx, w.idx2, (int)P, 0,
+                                               key_bits(m), s));
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)ceil_div(P, (int64_t)256)), dim3(256), 0, s, (const uint64_t *)w.key2, (const int32_t *)w.idx2, P,
+                       (const uint64_t *)nullptr, (const int64_t *)w.ids, (const float *)w.vals, ids, out_scores);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }

@@ -472,11 +472,7 @@ int mdx_rmac(const float *feat, int B, int C, int H, int W, const int32_t *regio
     MDX_CHECK_ARG(nregions >= 1 && nregions <= RMAC_MAX_REGIONS, "mdx_rmac: %d regions, 1..%d supported", nregions, RMAC_MAX_REGIONS);
     MDX_CHECK_ARG(eps >= 0.0f, "mdx_rmac: eps=%g", (double)eps);
     const int64_t need = mdx_rmac_workspace(B, C, nregions);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_rmac: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_rmac");
+    MDX_CHECK_WORKSPACE("mdx_rmac", workspace, workspace_bytes, need);
     RmacGrid grid;
     int rc = fill_grid(&grid, regions, nregions, H, W, "mdx_rmac");
     if (rc != MDX_OK) return rc;

@@ -1022,12 +1022,7 @@ static int rank_impl(const float *scores, int64_t n, int64_t nq, int64_t id_offs
                   (long long)nq);
     MDX_CHECK_ARG(n < (1ll << 32) && nq < 65536, "%s: n or nq too large", who);
     const int64_t need = carve(nullptr, nullptr, n, nq);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace %lld B < required %lld B", who, (long long)workspace_bytes,
-                  (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, who);
+    MDX_CHECK_WORKSPACE(who, workspace, workspace_bytes, need);
     RankWs ws;
     carve(&ws, (char *)workspace, n, nq);
     const bool arank = atomic_rank_ok(s);
@@ -1757,11 +1752,7 @@ int mdx_topk(const float *scores, int64_t n, int64_t nq, int64_t k, int64_t id_o
     MDX_CHECK_ARG(top_ids || top_scores, "mdx_topk: both outputs NULL");
     MDX_CHECK_ARG(scores && n > 0 && nq > 0 && n < (1ll << 32) && nq < 65536, "mdx_topk: bad sizes");
     const int64_t need = carve(nullptr, nullptr, n, nq);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_topk: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_topk");
+    MDX_CHECK_WORKSPACE("mdx_topk", workspace, workspace_bytes, need);
     const int route = topk_route(n, nq, k, workspace_bytes);
     if (route == MDX_TOPK_ROUTE_SAMPLED)
         return topk_sampled(scores, n, nq, k, id_offset, top_ids, top_scores, workspace, (hipStream_t)stream);

@@ -3,19 +3,16 @@
 //
 //   rescore_kernel   one workgroup per (query, tile of 64 candidates).  The 64 rows are gathered whole, 1 KiB of one row
 //                    per wave-instruction (no piece crosses a row), into a padded LDS tile; the next stage's pieces are in
-//                    flight in registers while wave 0 runs the chains (lane = candidate, k ascending, __builtin_fmaf from
-//                    +0, the query chunk broadcast from LDS).  k runs to round_up(d, 64) over zeros, as the fp32 MFMA
-//                    kernels of an index do, so the bits are those of mdx_scores on an fp32 index of the same rows.
+//                    flight in registers while wave 0 runs the chains (lane = candidate, the query chunk broadcast from
+//                    LDS).  The row loader, the stage arithmetic and the four-link chain step are those of mdx_exact.h, shared
+//                    with exact_kernel of mdx_join.hip: the bits are those of mdx_scores on an fp32 index of the same rows.
 //   rescore_sort     one workgroup per query: bitonic sort of up to 4096 (desc_key, id) pairs in LDS.
 //   certify_kernel   one workgroup per query: ||x_q||_1, the query's int8 scale, U_q and the certified depth.
 //   i8 bounds        a reduction over the codes and scales of an MDX_I8 shard (vector atomics of order-free max / min / or).
-#include "mdx_common.h"
+#include "mdx_exact.h"
 
 namespace mdx {
 namespace {
-
-typedef float rs_f32x4 __attribute__((ext_vector_type(4)));
-typedef int rs_i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RS_TC = 64;              // candidates per workgroup: one per lane of wave 0
 constexpr int RS_KC = 256;             // k per stage: one 1-KiB piece of every row
@@ -30,18 +27,6 @@ __device__ __forceinline__ float query_elem(const float *queries, int64_t nq, in
     if (k >= d) return 0.f;
     const float x = qlayout == MDX_ROW_MAJOR ? queries[q * d + k] : queries[k * nq + q];
     return center ? x - center[k] : x;
-}
-
-// floats 4 lane .. 4 lane + 3 of the stage's piece of one row (zeros beyond d; nothing read for an invalid row)
-__device__ __forceinline__ rs_f32x4 load_piece(const float *rows, int64_t id, int64_t ld, int64_t d, int64_t k, bool vec)
-{
-    rs_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (id < 0) return v;
-    const float *p = rows + id * ld;
-    if (vec && k + 4 <= d) return *(const rs_f32x4 *)(p + k);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = k + e < d ? p[k + e] : 0.f;
-    return v;
 }
 
 __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ rows, int64_t n, int64_t d, int64_t ld,
@@ -60,23 +45,22 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ 
         rid[tid] = (id >= 0 && id < n) ? id : -1;        // an id outside [0, n) is never dereferenced
     }
     __syncthreads();
-    const int64_t d_pad = (d + 63) / 64 * 64;
-    const int64_t stages = (d_pad + RS_KC - 1) / RS_KC;
+    const int64_t d_pad = chain_pad(d), stages = chain_stages(d_pad, RS_KC);
     int64_t my_ids[RS_ROWS_PER_WAVE];
 #pragma unroll
     for (int r = 0; r < RS_ROWS_PER_WAVE; ++r) my_ids[r] = rid[wave * RS_ROWS_PER_WAVE + r];
 
-    rs_f32x4 reg[RS_ROWS_PER_WAVE];
+    f32x4 reg[RS_ROWS_PER_WAVE];
     float qreg;
     auto fetch = [&](int64_t k0) {
 #pragma unroll
-        for (int r = 0; r < RS_ROWS_PER_WAVE; ++r) reg[r] = load_piece(rows, my_ids[r], ld, d, k0 + 4 * lane, vec);
+        for (int r = 0; r < RS_ROWS_PER_WAVE; ++r) reg[r] = row_piece(rows, my_ids[r], ld, d, k0 + 4 * lane, vec);
         qreg = query_elem(queries, nq, d, qlayout, center, q, k0 + tid);
     };
     auto put = [&]() {
 #pragma unroll
         for (int r = 0; r < RS_ROWS_PER_WAVE; ++r)
-            *(rs_f32x4 *)(tile + (wave * RS_ROWS_PER_WAVE + r) * RS_LD + 4 * lane) = reg[r];
+            *(f32x4 *)(tile + (wave * RS_ROWS_PER_WAVE + r) * RS_LD + 4 * lane) = reg[r];
         qs[tid] = qreg;
     };
 
@@ -88,15 +72,12 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ 
         const int64_t k0 = s * RS_KC;
         if (s + 1 < stages) fetch(k0 + RS_KC);                    // in flight during the chains
         if (wave == 0) {
-            const int kend = (int)(d_pad - k0 < RS_KC ? d_pad - k0 : RS_KC);     // a multiple of 64
+            const int kend = chain_kend(d_pad, k0, RS_KC);
             const float *x = tile + lane * RS_LD;
             for (int kk = 0; kk < kend; kk += 4) {
-                const rs_f32x4 xv = *(const rs_f32x4 *)(x + kk);
-                const rs_f32x4 qv = *(const rs_f32x4 *)(qs + kk);
-                acc = __builtin_fmaf(qv[0], xv[0], acc);
-                acc = __builtin_fmaf(qv[1], xv[1], acc);
-                acc = __builtin_fmaf(qv[2], xv[2], acc);
-                acc = __builtin_fmaf(qv[3], xv[3], acc);
+                const f32x4 xv = *(const f32x4 *)(x + kk);
+                const f32x4 qv = *(const f32x4 *)(qs + kk);
+                acc = chain_step4(acc, qv, xv);
             }
         }
         if (s + 1 < stages) {
@@ -170,22 +151,8 @@ __global__ __launch_bounds__(64) void i8_bounds_init_kernel(mdx_i8_bounds *b)
     }
 }
 
-__device__ __forceinline__ double wave_max_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ double wave_min_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // one wave per row tile (16 rows x KB tiles of 64 k): lane (g, j) sums |code| of row j over k groups g, the 4 groups add up
-__global__ __launch_bounds__(256) void i8_bounds_kernel(const rs_i32x4 *__restrict__ tiles, const float *__restrict__ scales, int64_t n,
+__global__ __launch_bounds__(256) void i8_bounds_kernel(const i32x4 *__restrict__ tiles, const float *__restrict__ scales, int64_t n,
                                                         int64_t RT, int64_t KB, mdx_i8_bounds *b)
 {
     const int64_t rt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -193,7 +160,7 @@ __global__ __launch_bounds__(256) void i8_bounds_kernel(const rs_i32x4 *__restri
     if (rt >= RT) return;                                        // wave-uniform
     uint32_t sum = 0;
     for (int64_t kb = 0; kb < KB; ++kb) {
-        const rs_i32x4 w = tiles[(rt * KB + kb) * 64 + lane];
+        const i32x4 w = tiles[(rt * KB + kb) * 64 + lane];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int c = (int)(int8_t)(uint8_t)((uint32_t)w[e >> 2] >> (8 * (e & 3)));
@@ -231,14 +198,6 @@ __global__ __launch_bounds__(256) void i8_bounds_kernel(const rs_i32x4 *__restri
 // ---------------------------------------------------------------- the certificate
 
 constexpr int CERT_THREADS = 256;
-
-// the next fp32 value above a finite x
-__device__ __forceinline__ float next_up(float x)
-{
-    if (x == 0.f) return __uint_as_float(1u);
-    const uint32_t u = __float_as_uint(x);
-    return __uint_as_float(x > 0.f ? u + 1 : u - 1);
-}
 
 __global__ __launch_bounds__(CERT_THREADS) void certify_kernel(const float *__restrict__ scores, int64_t K, const float *__restrict__ t,
                                                                const float *__restrict__ queries, int64_t nq, int64_t d, int qlayout,
@@ -354,11 +313,7 @@ int mdx_rescore(const float *rows, int64_t n, int64_t d, int64_t ld, const float
     const int64_t tiles = ceil_div(K, (int64_t)RS_TC);
     MDX_CHECK_ARG(nq * tiles < (1ll << 31), "mdx_rescore: nq=%lld too large for one launch", (long long)nq);
     const int64_t need = mdx_rescore_workspace(nq, K, d);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_rescore: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_rescore");
+    MDX_CHECK_WORKSPACE("mdx_rescore", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     float *sc = (float *)workspace;
     const bool vec = ld % 4 == 0 && ((uintptr_t)rows & 15) == 0;       // 16-byte pieces at 16-byte addresses
@@ -381,7 +336,7 @@ int mdx_index_i8_bounds(const mdx_index *index, mdx_i8_bounds *bounds, void *str
     MDX_CHECK_ARG(ceil_div(RT, (int64_t)4) < (1ll << 31), "mdx_index_i8_bounds: shard too large for one launch");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(i8_bounds_init_kernel, dim3(1), dim3(64), 0, s, bounds);
-    hipLaunchKernelGGL(i8_bounds_kernel, dim3((unsigned)ceil_div(RT, (int64_t)4)), dim3(256), 0, s, (const rs_i32x4 *)tiles, scales, n, RT,
+    hipLaunchKernelGGL(i8_bounds_kernel, dim3((unsigned)ceil_div(RT, (int64_t)4)), dim3(256), 0, s, (const i32x4 *)tiles, scales, n, RT,
                        KB, bounds);
     MDX_LAUNCH_CHECK();
     return MDX_OK;

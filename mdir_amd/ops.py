@@ -48,14 +48,32 @@ def _on(t):
     return torch.cuda.device(idx)
 
 
-def _dev(t, dtype, what):
+def _dev(t, dtype, what, contiguous=True):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("%s must be a CUDA/ROCm tensor: the MI355X path has no CPU fallback" % what)
     if t.dtype != dtype:
         raise TypeError("%s must be %s, got %s" % (what, dtype, t.dtype))
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError("%s must be contiguous" % what)
     return _vp(t.data_ptr())
+
+
+def _rows(t, what):
+    """(pointer, row stride) of a 2-D fp32 CUDA matrix whose rows are contiguous (a row slice of a larger matrix is fine)."""
+    p = _dev(t, torch.float32, what, contiguous=False)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        raise ValueError("%s must be a 2-d matrix with contiguous rows" % what)
+    return p, t.stride(0)
+
+
+def _center(center, d, dtype=torch.float32):
+    """Pointer of the optional ``center`` vector of ``d`` elements; None without one."""
+    if center is None:
+        return None
+    cp = _dev(center, dtype, "center")
+    if center.numel() != d:
+        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    return cp
 
 
 def _layout(t, layout, what):
@@ -467,9 +485,7 @@ class DescriptorIndex:
         if d != self.d:
             raise ValueError("query dimension %d != index dimension %d" % (d, self.d))
         qp = _dev(queries, torch.float32, "queries")
-        cp = _dev(center, torch.float32, "center") if center is not None else None
-        if center is not None and center.numel() != d:
-            raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+        cp = _center(center, d)
         if out is None:
             out = torch.empty((nq, self.n), dtype=torch.float32, device=self.device)
         elif tuple(out.shape) != (nq, self.n):
@@ -599,9 +615,7 @@ def scores_rowmajor(db, queries, qlayout="DN", center=None, out=None):
     if dq != d:
         raise ValueError("query dimension %d != database dimension %d" % (dq, d))
     qp = _dev(queries, torch.float32, "queries")
-    cp = _dev(center, torch.float32, "center") if center is not None else None
-    if center is not None and center.numel() != d:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    cp = _center(center, d)
     if out is None:
         out = torch.empty((nq, n), dtype=torch.float32, device=db.device)
     elif tuple(out.shape) != (nq, n):
@@ -662,9 +676,7 @@ def rescore(rows, queries, ids, qlayout="ND", center=None):
     if dq != d:
         raise ValueError("query dimension %d != rows dimension %d" % (dq, d))
     qp = _dev(queries, torch.float32, "queries")
-    cp = _dev(center, torch.float32, "center") if center is not None else None
-    if center is not None and center.numel() != d:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    cp = _center(center, d)
     _dev(ids, torch.int64, "ids")
     if ids.dim() != 2 or ids.shape[0] != nq:
         raise ValueError("ids must be [%d, K], got %s" % (nq, tuple(ids.shape)))
@@ -708,9 +720,7 @@ def rescore_certify(scores, t, queries, bounds, n, qlayout="ND", center=None):
     if nqq != nq:
         raise ValueError("queries hold %d queries, scores %d" % (nqq, nq))
     qp = _dev(queries, torch.float32, "queries")
-    cp = _dev(center, torch.float32, "center") if center is not None else None
-    if center is not None and center.numel() != d:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    cp = _center(center, d)
     bp = _dev(bounds, torch.float64, "bounds")
     if bounds.numel() != 4:
         raise ValueError("bounds: the float64 [4] tensor of DescriptorIndex.i8_bounds()")
@@ -740,6 +750,43 @@ def _tau(threshold):
     return t
 
 
+def _join_operands(who, a, stats_a, b, stats_b, a_lo, a_hi):
+    for name, ix in (("a", a), ("b", b)):
+        if not isinstance(ix, DescriptorIndex) or ix._h is None:
+            raise ValueError("%s: %s must be an open DescriptorIndex" % (who, name))
+        if ix.storage != "i8":
+            raise ValueError("%s: pruning needs int8 indexes (%s is %s)" % (who, name, ix.storage))
+    if a.d != b.d:
+        raise ValueError("%s: dimensions %d and %d differ" % (who, a.d, b.d))
+    a_hi = a.n if a_hi is None else int(a_hi)
+    a_lo = int(a_lo)
+    if not (0 <= a_lo < a_hi <= a.n) or a_lo % JOIN_BLOCK:
+        raise ValueError("%s: rows [%d, %d) of %d, the first a multiple of %d" % (who, a_lo, a_hi, a.n, JOIN_BLOCK))
+    for name, st, ix in (("stats_a", stats_a, a), ("stats_b", stats_b, b)):
+        _dev(st, torch.float32, name)
+        if tuple(st.shape) != (ix.n, 4):
+            raise ValueError("%s must be join_stats of its index: [%d, 4]" % (name, ix.n))
+    return a_lo, a_hi
+
+
+def _capacity(value):
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= _MAX_ITEMS:
+        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (value,))
+    return value
+
+
+def _pair_rows(rows_a, rows_b, m, m_lo, who):
+    """The operands of a resolve: (pointer, stride) of both row matrices, their dimension, and m, m_lo as checked ints."""
+    ap, lda = _rows(rows_a, "rows_a")
+    bp, ldb = _rows(rows_b, "rows_b")
+    if rows_a.shape[1] != rows_b.shape[1]:
+        raise ValueError("rows_a and rows_b differ in dimension")
+    m, m_lo = int(m), int(m_lo)
+    if m < 1 or m_lo < 0 or m > _MAX_ITEMS:
+        raise ValueError("%s: m=%d must be in [1, 2^31) and m_lo=%d >= 0" % (who, m, m_lo))
+    return ap, lda, bp, ldb, rows_a.shape[1], m, m_lo
+
+
 def center_rows(queries, qlayout="ND", center=None):
     """fp32 ``[nq, d]`` row-major: ``queries - center`` (one fp32 subtraction per element; a copy without ``center``) --
     the query rows ``x_q`` of a range search (``mdx_center_rows``)."""
@@ -747,9 +794,7 @@ def center_rows(queries, qlayout="ND", center=None):
     nq, d, lay = _layout(queries, qlayout, "queries")
     if nq < 1 or d < 1:
         raise ValueError("queries must be non-empty, got %d x %d" % (nq, d))
-    cp = _dev(center, torch.float32, "center") if center is not None else None
-    if center is not None and center.numel() != d:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    cp = _center(center, d)
     out = torch.empty((nq, d), dtype=torch.float32, device=queries.device)
     with _on(queries):
         check(_lib.lib().mdx_center_rows(qp, nq, d, lay, cp, _vp(out.data_ptr()), _stream()), "mdx_center_rows")
@@ -778,25 +823,10 @@ def join_candidates(a, stats_a, b, stats_b, threshold, a_lo=0, a_hi=None, symmet
     j > i).  ``count`` may exceed ``capacity``: then call again with ``capacity >= count``.  Synchronises the stream (reads
     the count)."""
     tau = _tau(threshold)
-    for name, ix in (("a", a), ("b", b)):
-        if not isinstance(ix, DescriptorIndex) or ix._h is None:
-            raise ValueError("join_candidates: %s must be an open DescriptorIndex" % name)
-        if ix.storage != "i8":
-            raise ValueError("join_candidates: pruning needs int8 indexes (%s is %s)" % (name, ix.storage))
-    if a.d != b.d:
-        raise ValueError("join_candidates: dimensions %d and %d differ" % (a.d, b.d))
+    a_lo, a_hi = _join_operands("join_candidates", a, stats_a, b, stats_b, a_lo, a_hi)
     if symmetric and a is not b:
         raise ValueError("join_candidates: the self-join joins one index with itself")
-    a_hi = a.n if a_hi is None else int(a_hi)
-    a_lo = int(a_lo)
-    if not (0 <= a_lo < a_hi <= a.n) or a_lo % JOIN_BLOCK:
-        raise ValueError("join_candidates: rows [%d, %d) of %d, the first a multiple of %d" % (a_lo, a_hi, a.n, JOIN_BLOCK))
-    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= _MAX_ITEMS:
-        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
-    for name, st, ix in (("stats_a", stats_a, a), ("stats_b", stats_b, b)):
-        _dev(st, torch.float32, name)
-        if tuple(st.shape) != (ix.n, 4):
-            raise ValueError("%s must be join_stats of its index: [%d, 4]" % (name, ix.n))
+    _capacity(capacity)
     pairs = torch.empty(max(capacity, 1), dtype=torch.int64, device=a.device)
     count = torch.zeros(1, dtype=torch.int64, device=a.device)
     with _on(pairs):
@@ -811,14 +841,7 @@ def join_resolve(rows_a, rows_b, pairs, threshold, m_lo, m):
     ``i << 32 | j``, unique, rows i in ``[m_lo, m_lo + m)``) of ``rows_a`` x ``rows_b``, the hits ``>= threshold`` and their CSR
     over rows ``m_lo ..`` in rank order (``mdx_join_resolve``).  Synchronises the stream (reads the hits)."""
     tau = _tau(threshold)
-    ap, lda = _rows(rows_a, "rows_a")
-    bp, ldb = _rows(rows_b, "rows_b")
-    if rows_a.shape[1] != rows_b.shape[1]:
-        raise ValueError("rows_a and rows_b differ in dimension")
-    d = rows_a.shape[1]
-    m, m_lo = int(m), int(m_lo)
-    if m < 1 or m_lo < 0 or m > _MAX_ITEMS:
-        raise ValueError("join_resolve: m=%d must be in [1, 2^31) and m_lo=%d >= 0" % (m, m_lo))
+    ap, lda, bp, ldb, d, m, m_lo = _pair_rows(rows_a, rows_b, m, m_lo, "join_resolve")
     dev = rows_a.device
     P = pairs.numel()
     if P == 0:
@@ -844,25 +867,6 @@ def join_resolve(rows_a, rows_b, pairs, threshold, m_lo, m):
 
 KNN_JOIN_MAX_K = 64               # include/mdx.h MDX_KNN_JOIN_MAX_K: the k largest bounds of 128 rows are kept in LDS
 KNN_MAX_SLICES = 64
-
-
-def _join_operands(who, a, stats_a, b, stats_b, a_lo, a_hi):
-    for name, ix in (("a", a), ("b", b)):
-        if not isinstance(ix, DescriptorIndex) or ix._h is None:
-            raise ValueError("%s: %s must be an open DescriptorIndex" % (who, name))
-        if ix.storage != "i8":
-            raise ValueError("%s: pruning needs int8 indexes (%s is %s)" % (who, name, ix.storage))
-    if a.d != b.d:
-        raise ValueError("%s: dimensions %d and %d differ" % (who, a.d, b.d))
-    a_hi = a.n if a_hi is None else int(a_hi)
-    a_lo = int(a_lo)
-    if not (0 <= a_lo < a_hi <= a.n) or a_lo % JOIN_BLOCK:
-        raise ValueError("%s: rows [%d, %d) of %d, the first a multiple of %d" % (who, a_lo, a_hi, a.n, JOIN_BLOCK))
-    for name, st, ix in (("stats_a", stats_a, a), ("stats_b", stats_b, b)):
-        _dev(st, torch.float32, name)
-        if tuple(st.shape) != (ix.n, 4):
-            raise ValueError("%s must be join_stats of its index: [%d, 4]" % (name, ix.n))
-    return a_lo, a_hi
 
 
 def _knn_k(who, k, nb=None):
@@ -901,8 +905,7 @@ def join_candidates_rows(a, stats_a, b, stats_b, taus, a_lo=0, a_hi=None, capaci
     tp = _dev(taus, torch.float32, "taus")
     if taus.dim() != 1 or taus.shape[0] != a_hi - a_lo or not taus.is_contiguous():
         raise ValueError("taus must be a contiguous [%d] tensor, one threshold per row" % (a_hi - a_lo))
-    if isinstance(capacity, bool) or not isinstance(capacity, int) or not 0 <= capacity <= _MAX_ITEMS:
-        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
+    _capacity(capacity)
     pairs = torch.empty(max(capacity, 1), dtype=torch.int64, device=a.device)
     count = torch.zeros(1, dtype=torch.int64, device=a.device)
     with _on(pairs):
@@ -918,14 +921,7 @@ def knn_resolve(rows_a, rows_b, pairs, m_lo, m, k):
     ``i << 32 | j``, unique, rows i in ``[m_lo, m_lo + m)``) of ``rows_a`` x ``rows_b`` and the first ``k`` of every row in rank
     order (``mdx_knn_resolve``); ``counts``: the candidates of each row -- where that is below k (thresholds that were not
     :func:`knn_bounds`') the tail is id -1 / score NaN."""
-    ap, lda = _rows(rows_a, "rows_a")
-    bp, ldb = _rows(rows_b, "rows_b")
-    if rows_a.shape[1] != rows_b.shape[1]:
-        raise ValueError("rows_a and rows_b differ in dimension")
-    d = rows_a.shape[1]
-    m, m_lo = int(m), int(m_lo)
-    if m < 1 or m_lo < 0 or m > _MAX_ITEMS:
-        raise ValueError("knn_resolve: m=%d must be in [1, 2^31) and m_lo=%d >= 0" % (m, m_lo))
+    ap, lda, bp, ldb, d, m, m_lo = _pair_rows(rows_a, rows_b, m, m_lo, "knn_resolve")
     k = _knn_k("knn_resolve", k)
     _dev(pairs, torch.int64, "pairs")
     P = pairs.numel()
@@ -955,9 +951,7 @@ def range_select(scores, threshold, diag=None, capacity=None):
         raise ValueError("range_select: scores must be non-empty, got %d x %d" % (m, n))
     if diag is not None and (isinstance(diag, bool) or not isinstance(diag, int) or diag < 0):
         raise ValueError("diag must be None or an integer >= 0, got %r" % (diag,))
-    cap = 1 << 16 if capacity is None else capacity
-    if isinstance(cap, bool) or not isinstance(cap, int) or not 0 <= cap <= _MAX_ITEMS:
-        raise ValueError("capacity must be an integer in [0, 2^31), got %r" % (capacity,))
+    cap = _capacity(1 << 16 if capacity is None else capacity)
     h = _lib.lib()
     dev = scores.device
     offsets = torch.empty(m + 1, dtype=torch.int64, device=dev)
@@ -975,17 +969,6 @@ def range_select(scores, threshold, diag=None, capacity=None):
         if hits > _MAX_ITEMS:
             raise ValueError("range_select: %d hits, more than one call holds (2^31 - 1)" % hits)
         cap = hits
-
-
-def _rows(t, what):
-    """(pointer, row stride) of a 2-D fp32 CUDA matrix whose rows are contiguous (a row slice of a larger matrix is fine)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA/ROCm tensor: the MI355X path has no CPU fallback" % what)
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be torch.float32, got %s" % (what, t.dtype))
-    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
-        raise ValueError("%s must be a 2-d matrix with contiguous rows" % what)
-    return _vp(t.data_ptr()), t.stride(0)
 
 
 def knn_aggregate(rows, ids, sims, alpha, self_rows=None, eps=1e-6, out=None):
@@ -1283,9 +1266,7 @@ def gram_f64(a, center=None):
     if a.dim() != 2:
         raise ValueError("a must be [d, n]")
     d, n = a.shape
-    cp = _dev(center, torch.float64, "center") if center is not None else None
-    if center is not None and center.numel() != d:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), d))
+    cp = _center(center, d, torch.float64)
     out = torch.empty((d, d), dtype=torch.float64, device=a.device)
     need = _lib.lib().mdx_gram_f64_workspace(d, n)
     ws = _workspace(need, a.device)
@@ -1311,9 +1292,7 @@ def project_f64(p, x, center=None):
     xp = _dev(x, torch.float64, "x")
     if p.dim() != 2 or x.dim() != 2 or p.shape[1] != x.shape[0]:
         raise ValueError("p [dout, d] and x [d, n] expected, got %s and %s" % (tuple(p.shape), tuple(x.shape)))
-    cp = _dev(center, torch.float64, "center") if center is not None else None
-    if center is not None and center.numel() != x.shape[0]:
-        raise ValueError("center has %d elements, expected %d" % (center.numel(), x.shape[0]))
+    cp = _center(center, x.shape[0], torch.float64)
     out = torch.empty((p.shape[0], x.shape[1]), dtype=torch.float64, device=x.device)
     need = _lib.lib().mdx_project_f64_workspace(p.shape[0], p.shape[1])
     ws = _workspace(need, x.device)
