@@ -24,11 +24,11 @@
  *  - Every function returns MDX_OK (0) or a negative mdx_status; the message of
  *    the last failure on the calling thread is mdx_last_error().  Nothing aborts.
  *  - One host thread per device at a time; handles are not internally locked.
- *  - Matrices are dense fp32.  "row-major [a,b]" means element (i,j) at i*b+j.
+ *  - Matrices are dense fp32 (the feature maps of section "fp16 trunk" excepted).  "row-major [a,b]" means element (i,j) at i*b+j.
  *
  * Alignment
  *    Every device pointer must be aligned to the size of ITS ELEMENT (4 bytes for float / int32, 8 for int64 / double, 2
- *    for int16, 1 for uint8 / int8) and to nothing more -- a row slice of a larger tensor is a legal argument and gives
+ *    for int16 / fp16, 1 for uint8 / int8) and to nothing more -- a row slice of a larger tensor is a legal argument and gives
  *    the same bits as an aligned copy (where a kernel has a 16-byte path it picks it by the address, or issues its 16-byte
  *    accesses at element alignment) -- except:
  *      pointer                                                     alignment   otherwise
@@ -233,6 +233,36 @@ int mdx_conv1x1_transpose_weights(const float *w, int64_t Cout, int64_t Cin, flo
 int mdx_conv1x1_bn_act(const float *x, const float *wt, int64_t N, int64_t Cin, int64_t Cout, int64_t HW, const float *mean,
                        const float *var, const float *weight, const float *bias, float eps, const float *residual, int relu,
                        float *out, void *stream);
+
+/* ------------------------------------------------------------------ fp16 trunk */
+
+/* The LABELLED half-precision mode of extraction (`precision: f16`, mdir_amd/networks.py): the convolutions run on fp16 feature
+ * maps (the library's, on the fp16 MFMA), the maps are held and moved as fp16, and everything from the pooling accumulator
+ * onwards is fp32 exactly as above.  fp32 remains the default and the parity contract; descriptors of an f16 trunk differ
+ * from fp32 ones by fp16 rounding of every layer's activations (tests/test_gpu_trunk_f16_e2e.py measures it against torch's own
+ * half path).  An element is an IEEE binary16; pointers are 2-byte aligned ("Alignment" above).  Two contracts:
+ *
+ * mdx_bn_act_f16      mdx_bn_act in place on an fp16 x (and an fp16 residual); mean, var, weight, bias stay C FLOATS.  Per
+ *                     element: x and the residual are converted to fp32 (exact), the five lines of mdx_bn_act run unchanged in
+ *                     fp32 (the + 0 without a residual and NaN through the ReLU included), and the result is rounded ONCE to
+ *                     fp16, to nearest even, overflow to +-inf as `Tensor.half()`.  So every element has one right value:
+ *                     oracle_bn_act(add_zero = 1) on the upcast input, then the conversion.  (torch's half bn / add / relu
+ *                     round three times.)  Vector path: 8 halves per 16-byte access when H*W % 8 == 0 and x / residual are
+ *                     16-byte aligned, the scalar path otherwise; the same split into launches of 65 535 planes.  Bit for bit
+ *                     in tests/test_gpu_bn_act_f16.py.
+ * mdx_pool_l2n_f16,   mdx_pool_l2n / mdx_pool_multi on fp16 maps, out / pooled fp32: BIT FOR BIT the value the fp32 entry point
+ * mdx_pool_multi_f16  returns on the same maps converted to fp32 -- for every H*W, kind, p and plane start (any multiple of 2
+ *                     bytes).  The kernels are the fp32 ones with another load: the same element-to-lane mapping and per-lane
+ *                     order, a lane's four consecutive elements now one 8-byte piece, (a + b) + (c + d), the same rule
+ *                     H*W % 4 == 0 for the pieces; MAC's NaN flag and GeM's clamp carry over.  tests/test_gpu_pool_f16.py.
+ * Not in this mode: mdx_conv1x1_bn_act (an f16 trunk leaves every convolution to the library, followed by mdx_bn_act_f16: the
+ * rule that picks the fp32 kernel rests on fp32 measurements), the input conversion, the thumbnail and the pyramid (fp32; a
+ * level is converted just before the trunk), R-MAC / regional pooling (they are given fp32 copies of the maps). */
+/* The prototypes of this section are in mdx_trunk_f16.h, beside this file, and their names in _lib.TRUNK_F16_EXPORTS, for the
+ * reason given under "exact kNN join" for mdx_knn_join.h: tests/test_cabi.py and tests/test_memguard_host.py pin the prototypes
+ * of THIS file.  Their census is tests/test_trunk_f16_host.py (exported, bound, and covered by
+ * tests/test_gpu_trunk_f16_memcontract.py). */
+#include "mdx_trunk_f16.h"
 
 /* Input conversion: uint8 images [B,H,W,C] (C = 1 or 3, interleaved) -> fp32 [B,C,H,W] with
  *   out = (u / 255 - mean[c]) / std[c]            (fp32, IEEE divisions, this operation order)

@@ -36,7 +36,7 @@ ABI_VERSION = 3        # include/mdx.h MDX_ABI_VERSION this binding was written 
 def build(force=False):
     """Compile libmdx.so with hipcc --offload-arch=gfx950 (see csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h")]
     stale = not os.path.exists(LIB_PATH) or \
         any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -100,6 +100,9 @@ def _declare(lib):
         "mdx_join_candidates_rows": (i32, [p, p, p, p, i64, i64, p, p, i64, p, p]),
         "mdx_knn_resolve_workspace": (i64, [i64, i64]),
         "mdx_knn_resolve": (i32, [p, i64, p, i64, i64, p, i64, i64, i64, i64, p, p, p, p, i64, p]),
+        "mdx_bn_act_f16": (i32, [p, p, i64, i64, i64, p, p, p, p, f32, i32, p]),
+        "mdx_pool_l2n_f16": (i32, [p, i32, i32, i32, i32, i32, f32, f32, f32, p, p]),
+        "mdx_pool_multi_f16": (i32, [pp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32, f32, f32, p, p]),
         "mdx_index_info": (i32, [p, pi64, pi64, pi64, pi64]),
         "mdx_scores_workspace": (i64, [i64, i64]),
         "mdx_quantize_i8": (i32, [p, i64, i64, i32, p, p, p]),
@@ -174,6 +177,10 @@ EXPORTS = ("mdx_abi_version", "mdx_last_error", "mdx_capture_recover", "mdx_rmac
 # tests/test_memguard_host.py pin EXPORTS to mdx.h's own prototypes and their number; tests/test_knn_join_host.py is the census
 # of these (include/mdx.h, "exact kNN join", says more)
 KNN_JOIN_EXPORTS = ("mdx_knn_bounds_workspace", "mdx_knn_bounds", "mdx_join_candidates_rows", "mdx_knn_resolve_workspace", "mdx_knn_resolve")
+
+# include/mdx_trunk_f16.h (included by mdx.h): the fp16 trunk mode, apart from EXPORTS for the same reason; the census of these is
+# tests/test_trunk_f16_host.py (include/mdx.h, "fp16 trunk")
+TRUNK_F16_EXPORTS = ("mdx_bn_act_f16", "mdx_pool_l2n_f16", "mdx_pool_multi_f16")
 
 
 def lib():

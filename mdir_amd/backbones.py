@@ -6,6 +6,11 @@ module trees below reproduce torchvision's child order and parameter names, so a
 reference ``state_dict`` (``features.0.weight``, ``features.4.0.conv1.weight`` ...)
 loads unchanged.  The convolutions themselves stay on PyTorch-ROCm / MIOpen: the
 backbone is not part of the hand-written hot path (BASELINE.json north_star).
+
+fp16 trunk (``precision: f16`` of ``networks.init_network``, a LABELLED mode: fp32 is the default and the parity contract).
+Parameters and state dicts stay fp32; a convolution applied to an fp16 input uses an fp16 copy of its weights cached on the
+module (``_conv``), and the epilogue is ``mdx_bn_act_f16`` with the BatchNorm statistics still fp32.  ``F16_ARCHITECTURES``
+lists what the mode covers.
 """
 import os
 
@@ -18,12 +23,36 @@ def _conv3x3(cin, cout, stride=1):
     return nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
 
 
+def _conv(conv, x, with_bias=True):
+    """``conv(x)`` -- every Conv2d call of the trunk goes through here.  An fp16 ``x`` meets an fp16 copy of the (fp32) weight
+    and bias, cached on the module and keyed like ``_mdx_wt`` below by WHICH tensor the parameter is (storage pointer, shape),
+    its in-place version and the device, so ``load_state_dict`` or an optimiser step rebuilds it; the parameters and the state
+    dict stay fp32.  A new copy is complete before it is cached, so streams other than the one that made it may read it.
+    ``with_bias=False``: the convolution alone (its bias is then the epilogue's shift)."""
+    if x.dtype != torch.float16 or conv.weight.dtype == torch.float16:
+        return conv(x) if with_bias or conv.bias is None else conv._conv_forward(x, conv.weight, None)
+    w, b = conv.weight, conv.bias
+    key = (w.data_ptr(), tuple(w.shape), w._version, x.device) + (() if b is None else (b.data_ptr(), b._version))
+    h = getattr(conv, "_mdx_w16", None)
+    if h is None or h[0] != key:
+        h = (key, w.detach().to(x.device, torch.float16), None if b is None else b.detach().to(x.device, torch.float16))
+        # the scales of a pyramid run on streams of their own (graphs.parallel_map) and all of them read this copy, which the
+        # stream that got here first has just made: finish it before anybody else can be launched (once per convolution and
+        # weight change; never inside a capture, whose eager warm-up pass has been here before)
+        if x.is_cuda and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(x.device).synchronize()
+        conv._mdx_w16 = h
+    return conv._conv_forward(x, h[1], h[2] if with_bias else None)
+
+
 def _bn_act(x, bn, residual=None, relu=True):
     """``relu(bn(x) + residual)`` on a fresh convolution output.  At inference on the GPU the three
     full-tensor passes are one in-place kernel (``mdx_bn_act``: a third of the trunk's GPU time and
-    400 of its 1100 launches on ResNet101); training / CPU tensors / autograd keep the module calls."""
+    400 of its 1100 launches on ResNet101; ``mdx_bn_act_f16`` on fp16 maps, which rounds once where the module calls round
+    three times); training / CPU tensors / autograd keep the module calls (on fp16 maps with fp32 BatchNorm parameters:
+    torch's own mixed case)."""
     if (x.is_cuda and not bn.training and not torch.is_grad_enabled() and bn.track_running_stats
-            and x.dtype == torch.float32 and _fused_trunk()):
+            and x.dtype in (torch.float32, torch.float16) and _fused_trunk()):
         from . import ops
         res = residual.contiguous() if residual is not None else None
         return ops.bn_act_(x.contiguous(), bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, res, relu)
@@ -43,7 +72,9 @@ def _own_conv1x1(conv, residual):
     do not depend on a measurement): the expand convolutions (the ones that add the identity: K is short and the epilogue pass
     they save costs as much as the GEMM) and convolutions with <= 64 output channels (MIOpen's choice there runs at 40 TFLOP/s);
     the long-K reduce convolutions stay with the library GEMM, which runs at 110-135 TFLOP/s against 95-100 here
-    (``profiles/r03_conv1x1.md``).  ``1`` = every supported one, ``0`` = none."""
+    (``profiles/r03_conv1x1.md``).  ``1`` = every supported one, ``0`` = none.
+    fp32 only: those measurements do not exist for fp16, and ``mdx_conv1x1_bn_act`` has no fp16 form, so an fp16 trunk leaves
+    EVERY convolution to the library and follows it with ``mdx_bn_act_f16`` (``_conv_bn_act`` never asks this rule there)."""
     mode = os.environ.get("MDIR_AMD_CONV1X1", "auto")
     if mode == "0":
         return False
@@ -69,12 +100,12 @@ def _conv_bn_act(conv, bn, x, residual=None, relu=True):
                 conv._mdx_wt = wt
             res = residual.contiguous() if residual is not None else None
             return ops.conv1x1_bn_act(x.contiguous(), wt[1], bn.running_mean, bn.running_var, bn.weight, bn.bias, bn.eps, res, relu)
-    return _bn_act(conv(x), bn, residual, relu)
+    return _bn_act(_conv(conv, x), bn, residual, relu)
 
 
 def _downsample(mod, x):
-    if isinstance(mod, nn.Sequential) and len(mod) == 2 and isinstance(mod[1], nn.BatchNorm2d):
-        return _bn_act(mod[0](x), mod[1], None, relu=False)
+    if isinstance(mod, nn.Sequential) and len(mod) == 2 and isinstance(mod[0], nn.Conv2d) and isinstance(mod[1], nn.BatchNorm2d):
+        return _bn_act(_conv(mod[0], x), mod[1], None, relu=False)
     return mod(x)
 
 
@@ -92,8 +123,8 @@ class BasicBlock(nn.Module):
 
     def forward(self, x):
         idt = x if self.downsample is None else _downsample(self.downsample, x)
-        out = _bn_act(self.conv1(x), self.bn1)
-        return _bn_act(self.conv2(out), self.bn2, idt)
+        out = _bn_act(_conv(self.conv1, x), self.bn1)
+        return _bn_act(_conv(self.conv2, out), self.bn2, idt)
 
 
 class Bottleneck(nn.Module):
@@ -113,7 +144,7 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         idt = x if self.downsample is None else _downsample(self.downsample, x)
         out = _conv_bn_act(self.conv1, self.bn1, x)
-        out = _bn_act(self.conv2(out), self.bn2)
+        out = _bn_act(_conv(self.conv2, out), self.bn2)
         return _conv_bn_act(self.conv3, self.bn3, out, idt)
 
 
@@ -121,10 +152,14 @@ class TrunkSequential(nn.Sequential):
     """``nn.Sequential`` (same child names, same state dict) whose inference pass on the GPU folds
     the elementwise modules that follow a convolution into one in-place kernel:
     ``Conv2d(bias=False) -> BatchNorm2d [-> ReLU]`` (ResNet stem) and ``Conv2d(bias) -> ReLU``
-    (every VGG / AlexNet layer: the bias add and the ReLU are two full-tensor passes otherwise)."""
+    (every VGG / AlexNet layer: the bias add and the ReLU are two full-tensor passes otherwise).  fp16 input: the same
+    folding through ``mdx_bn_act_f16``; unfused (``MDIR_AMD_FUSED_TRUNK=0``) the modules in order, the convolutions through
+    ``_conv``."""
 
     def forward(self, x):
-        if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and _fused_trunk()):
+        half = x.dtype == torch.float16
+        fused = x.is_cuda and (half or x.dtype == torch.float32) and not torch.is_grad_enabled() and _fused_trunk()
+        if not fused and not half:
             return super().forward(x)
         from . import ops
         mods = list(self)
@@ -132,19 +167,18 @@ class TrunkSequential(nn.Sequential):
         while i < len(mods):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            if isinstance(m, nn.Conv2d) and m.padding_mode == "zeros" and not isinstance(m.padding, str):
+            if fused and isinstance(m, nn.Conv2d) and m.padding_mode == "zeros" and not isinstance(m.padding, str):
                 if (m.bias is None and isinstance(nxt, nn.BatchNorm2d) and not nxt.training and nxt.track_running_stats):
                     relu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.ReLU)
-                    x = ops.bn_act_(m(x).contiguous(), nxt.running_mean, nxt.running_var, nxt.weight, nxt.bias, nxt.eps,
+                    x = ops.bn_act_(_conv(m, x).contiguous(), nxt.running_mean, nxt.running_var, nxt.weight, nxt.bias, nxt.eps,
                                     None, relu)
                     i += 3 if relu else 2
                     continue
                 if m.bias is not None and isinstance(nxt, nn.ReLU):
-                    y = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
-                    x = ops.bn_act_(y.contiguous(), None, None, None, m.bias, 0.0, None, True)
+                    x = ops.bn_act_(_conv(m, x, with_bias=False).contiguous(), None, None, None, m.bias, 0.0, None, True)
                     i += 2
                     continue
-            x = m(x)
+            x = _conv(m, x) if isinstance(m, nn.Conv2d) else m(x)
             i += 1
         return x
 
@@ -290,6 +324,21 @@ OUTPUT_DIM = {"alexnet": 256, "vgg11": 512, "vgg13": 512, "vgg16": 512, "vgg19":
               "resnet34": 512, "resnet50": 2048, "resnet101": 2048, "resnet152": 2048,
               "densenet121": 1024, "densenet169": 1664, "densenet201": 1920, "densenet161": 2208,
               "squeezenet1_0": 512, "squeezenet1_1": 512}
+
+
+# what the fp16 trunk covers: the stacks whose every convolution goes through `_conv` (DenseNet's and SqueezeNet's blocks call
+# their modules directly and concatenate maps; they stay fp32-only)
+F16_ARCHITECTURES = frozenset(["alexnet"]) | frozenset(_VGG) | frozenset(_RESNET)
+
+
+def check_precision(architecture, precision):
+    """``precision`` as ``init_network`` accepts it: "f32" (the default and the parity contract) or "f16" (labelled)."""
+    if isinstance(precision, bool) or precision not in ("f32", "f16"):
+        raise ValueError("precision: 'f32' or 'f16', got %r" % (precision,))
+    if precision == "f16" and architecture not in F16_ARCHITECTURES:
+        raise ValueError("precision 'f16' is limited to %s: the blocks of '%s' do not route their convolutions through the fp16 "
+                         "weight copies" % (", ".join(sorted(F16_ARCHITECTURES)), architecture))
+    return precision
 
 
 def build_features(architecture):

@@ -8,6 +8,8 @@
 // CirMultiscaleAggregation.aggregate_tensor (mdir/components/data/wrapper.py:109-119).
 #include <math.h>
 
+#include <hip/hip_fp16.h>
+
 #include "mdx_common.h"
 
 namespace mdx {
@@ -39,17 +41,18 @@ __device__ __forceinline__ float max_or_nan(float wave_maximum, bool lane_saw_na
     return __any(lane_saw_nan) ? __builtin_nanf("") : wave_maximum;
 }
 
-// a lane's part of a plane read in 16-byte pieces: the order of the sum is the same for both vector types
-template <int KIND, int MODE, typename V4>
-__device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int HW, float p, float eps, int lane, float acc,
+// a lane's part of a plane read in pieces of four elements (16 bytes of fp32, 8 of fp16; a half converts exactly): the order
+// of the sum is the same for every vector type, so fp16 maps pool to the bits of their fp32 copies (mdx_pool_l2n_f16)
+template <int KIND, int MODE, typename V4, typename T>
+__device__ __forceinline__ float pool_pieces(const T *__restrict__ src, int HW, float p, float eps, int lane, float acc,
                                              bool &saw_nan)
 {
     const V4 *s4 = (const V4 *)src;
     const int n4 = HW >> 2;
     for (int i = lane; i < n4; i += 64) {
         const V4 v = s4[i];
-        const float a = pool_elem<KIND, MODE>(v.x, p, eps), b = pool_elem<KIND, MODE>(v.y, p, eps);
-        const float c = pool_elem<KIND, MODE>(v.z, p, eps), d = pool_elem<KIND, MODE>(v.w, p, eps);
+        const float a = pool_elem<KIND, MODE>((float)v.x, p, eps), b = pool_elem<KIND, MODE>((float)v.y, p, eps);
+        const float c = pool_elem<KIND, MODE>((float)v.z, p, eps), d = pool_elem<KIND, MODE>((float)v.w, p, eps);
         if (KIND == MDX_POOL_MAC) {
             acc = fmaxf(acc, fmaxf(fmaxf(a, b), fmaxf(c, d)));
             saw_nan |= (a != a) | (b != b) | (c != c) | (d != d);
@@ -60,23 +63,43 @@ __device__ __forceinline__ float pool_pieces(const float *__restrict__ src, int 
     return acc;
 }
 
-// one wave reduces one (image, channel) plane; every lane returns the pooled value
+// the four-element pieces of a wide plane: fp32 in 16-byte loads (at dword alignment off the 16-byte grid), fp16 in 8-byte
+// loads (at 2-byte alignment off the 8-byte grid)
 template <int KIND, int MODE>
-__device__ __forceinline__ float pool_plane(const float *__restrict__ src, bool wide, int HW, float p, float inv_p, float eps,
+__device__ __forceinline__ float pool_wide(const float *__restrict__ src, int HW, float p, float eps, int lane, float acc, bool &saw_nan)
+{
+    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+    if (((uintptr_t)src & 15) == 0) return pool_pieces<KIND, MODE, float4>(src, HW, p, eps, lane, acc, saw_nan);
+    return pool_pieces<KIND, MODE, f32x4u>(src, HW, p, eps, lane, acc, saw_nan);
+}
+
+template <int KIND, int MODE>
+__device__ __forceinline__ float pool_wide(const __half *__restrict__ src, int HW, float p, float eps, int lane, float acc, bool &saw_nan)
+{
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4), aligned(8)));
+    typedef _Float16 f16x4u __attribute__((ext_vector_type(4), aligned(2)));
+    if (((uintptr_t)src & 7) == 0) return pool_pieces<KIND, MODE, f16x4>(src, HW, p, eps, lane, acc, saw_nan);
+    return pool_pieces<KIND, MODE, f16x4u>(src, HW, p, eps, lane, acc, saw_nan);
+}
+
+__device__ __forceinline__ float pool_load(float v) { return v; }
+__device__ __forceinline__ float pool_load(__half v) { return __half2float(v); }
+
+// one wave reduces one (image, channel) plane; every lane returns the pooled value
+template <int KIND, int MODE, typename T>
+__device__ __forceinline__ float pool_plane(const T *__restrict__ src, bool wide, int HW, float p, float inv_p, float eps,
                                             int lane)
 {
     float acc = KIND == MDX_POOL_MAC ? -INFINITY : 0.0f;
     bool saw_nan = false;
     if (wide) {
-        // H*W % 4 == 0.  The plane of a sliced feature map starts at any multiple of 4 bytes; the summation order (hence
-        // every bit of the result) must not depend on where the caller's tensor lies, so a plane off the 16-byte grid is
-        // read in the same pieces through 16-byte loads at dword alignment
-        typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-        if (((uintptr_t)src & 15) == 0) acc = pool_pieces<KIND, MODE, float4>(src, HW, p, eps, lane, acc, saw_nan);
-        else acc = pool_pieces<KIND, MODE, f32x4u>(src, HW, p, eps, lane, acc, saw_nan);
+        // H*W % 4 == 0.  The plane of a sliced feature map starts at any multiple of its element size; the summation order
+        // (hence every bit of the result) must not depend on where the caller's tensor lies, so a plane off the grid of
+        // its loads is read in the same pieces through the same loads at element alignment
+        acc = pool_wide<KIND, MODE>(src, HW, p, eps, lane, acc, saw_nan);
     } else {
         for (int i = lane; i < HW; i += 64) {
-            const float a = pool_elem<KIND, MODE>(src[i], p, eps);
+            const float a = pool_elem<KIND, MODE>(pool_load(src[i]), p, eps);
             if (KIND == MDX_POOL_MAC) {
                 acc = fmaxf(acc, a);
                 saw_nan |= a != a;
@@ -92,8 +115,8 @@ __device__ __forceinline__ float pool_plane(const float *__restrict__ src, bool 
     return r;
 }
 
-template <int KIND, int MODE>
-__global__ __launch_bounds__(256) void pool_kernel(const float *__restrict__ feat, int64_t planes,
+template <int KIND, int MODE, typename T>
+__global__ __launch_bounds__(256) void pool_kernel(const T *__restrict__ feat, int64_t planes,
                                                    int HW, float p, float inv_p, float eps,
                                                    float *__restrict__ out)
 {
@@ -107,14 +130,15 @@ __global__ __launch_bounds__(256) void pool_kernel(const float *__restrict__ fea
 
 // The S feature maps of an image pyramid ([B,C,H_s,W_s] each) pooled by ONE launch: plane index -> (scale, image,
 // channel); out [S,B,C].  Same per-plane arithmetic as pool_kernel.
+template <typename T>
 struct PoolMaps {
-    const float *feat[8];
+    const T *feat[8];
     int hw[8];
     int64_t first[9];           // first plane of scale s; first[S] = all planes
 };
 
-template <int KIND, int MODE>
-__global__ __launch_bounds__(256) void pool_multi_kernel(PoolMaps maps, int S, float p, float inv_p, float eps,
+template <int KIND, int MODE, typename T>
+__global__ __launch_bounds__(256) void pool_multi_kernel(PoolMaps<T> maps, int S, float p, float inv_p, float eps,
                                                          float *__restrict__ out)
 {
     const int lane = threadIdx.x & 63;
@@ -122,7 +146,7 @@ __global__ __launch_bounds__(256) void pool_multi_kernel(PoolMaps maps, int S, f
     if (plane >= maps.first[S]) return;
     int s = 0;
     while (s + 1 < S && plane >= maps.first[s + 1]) ++s;
-    const float *feat = maps.feat[s];
+    const T *feat = maps.feat[s];
     const int HW = maps.hw[s];
     const bool wide = (HW & 3) == 0;
     const float r = pool_plane<KIND, MODE>(feat + (plane - maps.first[s]) * HW, wide, HW, p, inv_p, eps, lane);
@@ -266,30 +290,30 @@ __global__ __launch_bounds__(1024) void l2n_aggregate_kernel(const float *__rest
     for (int64_t k = tid; k < D; k += 1024) dst[k] = dst[k] / nrm;
 }
 
-template <int KIND>
-static void launch_pool_multi(int mode, const PoolMaps &maps, int S, float p, float eps, float *out, hipStream_t s)
+template <int KIND, typename T>
+static void launch_pool_multi(int mode, const PoolMaps<T> &maps, int S, float p, float eps, float *out, hipStream_t s)
 {
     const dim3 grid((unsigned)ceil_div(maps.first[S], 4)), blk(256);
     const float inv_p = 1.0f / p;
     switch (mode) {
-        case 1: hipLaunchKernelGGL((pool_multi_kernel<KIND, 1>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
-        case 2: hipLaunchKernelGGL((pool_multi_kernel<KIND, 2>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
-        case 3: hipLaunchKernelGGL((pool_multi_kernel<KIND, 3>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
-        default: hipLaunchKernelGGL((pool_multi_kernel<KIND, 0>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
+        case 1: hipLaunchKernelGGL((pool_multi_kernel<KIND, 1, T>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
+        case 2: hipLaunchKernelGGL((pool_multi_kernel<KIND, 2, T>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
+        case 3: hipLaunchKernelGGL((pool_multi_kernel<KIND, 3, T>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
+        default: hipLaunchKernelGGL((pool_multi_kernel<KIND, 0, T>), grid, blk, 0, s, maps, S, p, inv_p, eps, out); break;
     }
 }
 
-template <int KIND>
-static void launch_pool(int mode, const float *feat, int64_t planes, int HW, float p, float eps,
+template <int KIND, typename T>
+static void launch_pool(int mode, const T *feat, int64_t planes, int HW, float p, float eps,
                         float *out, hipStream_t s)
 {
     const dim3 grid((unsigned)ceil_div(planes, 4)), blk(256);
     const float inv_p = 1.0f / p;
     switch (mode) {
-        case 1: hipLaunchKernelGGL((pool_kernel<KIND, 1>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
-        case 2: hipLaunchKernelGGL((pool_kernel<KIND, 2>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
-        case 3: hipLaunchKernelGGL((pool_kernel<KIND, 3>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
-        default: hipLaunchKernelGGL((pool_kernel<KIND, 0>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
+        case 1: hipLaunchKernelGGL((pool_kernel<KIND, 1, T>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
+        case 2: hipLaunchKernelGGL((pool_kernel<KIND, 2, T>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
+        case 3: hipLaunchKernelGGL((pool_kernel<KIND, 3, T>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
+        default: hipLaunchKernelGGL((pool_kernel<KIND, 0, T>), grid, blk, 0, s, feat, planes, HW, p, inv_p, eps, out); break;
     }
 }
 
@@ -310,29 +334,45 @@ int mdx_l2n_rows(float *x, int64_t R, int64_t D, const float *bias, float eps, v
     return MDX_OK;
 }
 
-int mdx_pool_l2n(const float *feat, int B, int C, int H, int W, int kind, float p, float pool_eps,
-                 float l2n_eps, float *out, void *stream)
+// mdx_pool_l2n / mdx_pool_l2n_f16 (`who`): T = the element of the maps
+extern "C++" {
+template <typename T>
+static int pool_l2n(const char *who, const T *feat, int B, int C, int H, int W, int kind, float p, float pool_eps, float l2n_eps, float *out,
+                    void *stream)
 {
-    MDX_CHECK_ARG(feat && out, "mdx_pool_l2n: NULL pointer");
-    MDX_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "mdx_pool_l2n: bad shape [%d,%d,%d,%d]", B, C, H, W);
-    MDX_CHECK_ARG((int64_t)H * W < (1ll << 31), "mdx_pool_l2n: H*W too large");
+    MDX_CHECK_ARG(feat && out, "%s: NULL pointer", who);
+    MDX_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "%s: bad shape [%d,%d,%d,%d]", who, B, C, H, W);
+    MDX_CHECK_ARG((int64_t)H * W < (1ll << 31), "%s: H*W too large", who);
     hipStream_t s = (hipStream_t)stream;
     const int64_t planes = (int64_t)B * C;
     const int HW = H * W;
     switch (kind) {
         case MDX_POOL_GEM: {
-            MDX_CHECK_ARG(p > 0.0f && pool_eps > 0.0f, "mdx_pool_l2n: gem needs p > 0 and eps > 0");
+            MDX_CHECK_ARG(p > 0.0f && pool_eps > 0.0f, "%s: gem needs p > 0 and eps > 0", who);
             const int mode = p == 1.0f ? 1 : p == 2.0f ? 2 : p == 3.0f ? 3 : 0;
             launch_pool<MDX_POOL_GEM>(mode, feat, planes, HW, p, pool_eps, out, s);
             break;
         }
         case MDX_POOL_MAC: launch_pool<MDX_POOL_MAC>(1, feat, planes, HW, 1.0f, 0.0f, out, s); break;
         case MDX_POOL_SPOC: launch_pool<MDX_POOL_SPOC>(1, feat, planes, HW, 1.0f, 0.0f, out, s); break;
-        default: MDX_CHECK_ARG(false, "mdx_pool_l2n: unknown pooling kind %d", kind);
+        default: MDX_CHECK_ARG(false, "%s: unknown pooling kind %d", who, kind);
     }
     MDX_LAUNCH_CHECK();
     if (l2n_eps >= 0.0f) return mdx_l2n_rows(out, B, C, nullptr, l2n_eps, stream);
     return MDX_OK;
+}
+}   // extern "C++"
+
+int mdx_pool_l2n(const float *feat, int B, int C, int H, int W, int kind, float p, float pool_eps,
+                 float l2n_eps, float *out, void *stream)
+{
+    return pool_l2n("mdx_pool_l2n", feat, B, C, H, W, kind, p, pool_eps, l2n_eps, out, stream);
+}
+
+int mdx_pool_l2n_f16(const __half *feat, int B, int C, int H, int W, int kind, float p, float pool_eps,
+                     float l2n_eps, float *out, void *stream)
+{
+    return pool_l2n("mdx_pool_l2n_f16", feat, B, C, H, W, kind, p, pool_eps, l2n_eps, out, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -484,20 +524,23 @@ int mdx_rmac(const float *feat, int B, int C, int H, int W, const int32_t *regio
     return MDX_OK;
 }
 
-int mdx_pool_multi(const float *const *feats, int S, int B, int C, const int *H, const int *W, int kind, float p,
-                   float pool_eps, float *pooled, void *stream)
+// mdx_pool_multi / mdx_pool_multi_f16 (`who`): T = the element of the maps
+extern "C++" {
+template <typename T>
+static int pool_multi(const char *who, const T *const *feats, int S, int B, int C, const int *H, const int *W, int kind, float p,
+                      float pool_eps, float *pooled, void *stream)
 {
-    MDX_CHECK_ARG(feats && H && W && pooled, "mdx_pool_multi: NULL pointer");
-    MDX_CHECK_ARG(S >= 1 && S <= 8, "mdx_pool_multi: S=%d not in 1..8", S);
-    MDX_CHECK_ARG(B > 0 && C > 0, "mdx_pool_multi: bad batch/channels [%d,%d]", B, C);
-    PoolMaps maps;
+    MDX_CHECK_ARG(feats && H && W && pooled, "%s: NULL pointer", who);
+    MDX_CHECK_ARG(S >= 1 && S <= 8, "%s: S=%d not in 1..8", who, S);
+    MDX_CHECK_ARG(B > 0 && C > 0, "%s: bad batch/channels [%d,%d]", who, B, C);
+    PoolMaps<T> maps;
     maps.first[0] = 0;
     for (int s = 0; s < 8; ++s) {
         maps.feat[s] = s < S ? feats[s] : nullptr;
         maps.hw[s] = 0;
         if (s < S) {
-            MDX_CHECK_ARG(feats[s], "mdx_pool_multi: map %d is NULL", s);
-            MDX_CHECK_ARG(H[s] > 0 && W[s] > 0 && (int64_t)H[s] * W[s] < (1ll << 31), "mdx_pool_multi: bad map size %d x %d", H[s], W[s]);
+            MDX_CHECK_ARG(feats[s], "%s: map %d is NULL", who, s);
+            MDX_CHECK_ARG(H[s] > 0 && W[s] > 0 && (int64_t)H[s] * W[s] < (1ll << 31), "%s: bad map size %d x %d", who, H[s], W[s]);
             maps.hw[s] = H[s] * W[s];
         }
         maps.first[s + 1] = maps.first[s] + (s < S ? (int64_t)B * C : 0);
@@ -505,17 +548,30 @@ int mdx_pool_multi(const float *const *feats, int S, int B, int C, const int *H,
     hipStream_t st = (hipStream_t)stream;
     switch (kind) {
         case MDX_POOL_GEM: {
-            MDX_CHECK_ARG(p > 0.0f && pool_eps > 0.0f, "mdx_pool_multi: gem needs p > 0 and eps > 0");
+            MDX_CHECK_ARG(p > 0.0f && pool_eps > 0.0f, "%s: gem needs p > 0 and eps > 0", who);
             const int mode = p == 1.0f ? 1 : p == 2.0f ? 2 : p == 3.0f ? 3 : 0;
             launch_pool_multi<MDX_POOL_GEM>(mode, maps, S, p, pool_eps, pooled, st);
             break;
         }
         case MDX_POOL_MAC: launch_pool_multi<MDX_POOL_MAC>(1, maps, S, 1.0f, 0.0f, pooled, st); break;
         case MDX_POOL_SPOC: launch_pool_multi<MDX_POOL_SPOC>(1, maps, S, 1.0f, 0.0f, pooled, st); break;
-        default: MDX_CHECK_ARG(false, "mdx_pool_multi: unknown pooling kind %d", kind);
+        default: MDX_CHECK_ARG(false, "%s: unknown pooling kind %d", who, kind);
     }
     MDX_LAUNCH_CHECK();
     return MDX_OK;
+}
+}   // extern "C++"
+
+int mdx_pool_multi(const float *const *feats, int S, int B, int C, const int *H, const int *W, int kind, float p,
+                   float pool_eps, float *pooled, void *stream)
+{
+    return pool_multi("mdx_pool_multi", feats, S, B, C, H, W, kind, p, pool_eps, pooled, stream);
+}
+
+int mdx_pool_multi_f16(const __half *const *feats, int S, int B, int C, const int *H, const int *W, int kind, float p,
+                       float pool_eps, float *pooled, void *stream)
+{
+    return pool_multi("mdx_pool_multi_f16", feats, S, B, C, H, W, kind, p, pool_eps, pooled, stream);
 }
 
 int mdx_l2n_aggregate(const float *pooled, int S, int64_t B, int64_t D, float l2n_eps, float msp, float *out,

@@ -8,6 +8,8 @@
 // (read+write).  On ResNet101 at 1024x768 that is 711 launches and a third of the trunk's GPU time,
 // and the trunk is launch-bound on top.  HBM-bound: one read (+ one for the residual) and one write
 // per element.
+#include <hip/hip_fp16.h>
+
 #include "mdx_common.h"
 
 namespace mdx {
@@ -29,66 +31,100 @@ __device__ __forceinline__ void bn_coeffs(const BnArgs &a, int c, float &mean, f
 __device__ __forceinline__ float relu_keep_nan(float y) { return y < 0.0f ? 0.0f : y; }
 
 // One workgroup = a run of one (image, channel) plane, so the four per-channel statistics are
-// scalar loads and no thread divides anything.  VEC = 4: planes are a multiple of 4 long and 16-B
-// aligned (float4 accesses); VEC = 1 covers odd plane sizes.  Each thread takes UNR elements, all
-// loads issued before the first store.
+// scalar loads and no thread divides anything.  T: the element, fp32 or fp16 (mdx_bn_act_f16: the statistics and
+// the arithmetic stay fp32, the result is rounded once).  VECTOR: planes are a multiple of one 16-byte access long
+// (4 floats, 8 halves) and 16-B aligned; the scalar form covers every other plane size.  Each thread takes UNR
+// accesses, all loads issued before the first store.
 constexpr int BN_UNR = 4;
 
-template <int VEC, bool RES, bool RELU>
-__global__ __launch_bounds__(256) void bn_act_kernel(float *__restrict__ x, const float *__restrict__ res,
+template <typename T> struct alignas(16) BnPack { T e[16 / sizeof(T)]; };
+
+__device__ __forceinline__ float bn_load(float v) { return v; }
+__device__ __forceinline__ float bn_load(__half v) { return __half2float(v); }                  // exact
+__device__ __forceinline__ void bn_store(float &dst, float v) { dst = v; }
+__device__ __forceinline__ void bn_store(__half &dst, float v) { dst = __float2half_rn(v); }    // to nearest even; overflow -> inf
+
+template <bool RES, bool RELU>
+__device__ __forceinline__ float bn_elem(float v, float r, float mean, float scale, float shift)
+{
+    const float o = fmaf(v - mean, scale, shift) + (RES ? r : 0.0f);
+    return RELU ? relu_keep_nan(o) : o;
+}
+
+template <typename T, bool VECTOR, bool RES, bool RELU>
+__global__ __launch_bounds__(256) void bn_act_kernel(T *__restrict__ x, const T *__restrict__ res,
                                                      int64_t plane0, unsigned hw_vec, unsigned C, BnArgs a)
 {
+    typedef BnPack<T> Pack;
+    constexpr int N = 16 / sizeof(T);
     const int64_t plane = plane0 + blockIdx.y;
     float mean, scale, shift;
     bn_coeffs(a, (int)(plane % C), mean, scale, shift);
     const int64_t base = plane * hw_vec;
     const unsigned i0 = blockIdx.x * (256 * BN_UNR) + threadIdx.x;
-    if (VEC == 4) {
-        float4 v[BN_UNR], r[BN_UNR];
+    if (VECTOR) {
+        Pack v[BN_UNR], r[BN_UNR];
 #pragma unroll
         for (int u = 0; u < BN_UNR; ++u) {
             const unsigned i = i0 + u * 256;
             if (i < hw_vec) {
-                v[u] = ((const float4 *)x)[base + i];
-                if (RES) r[u] = ((const float4 *)res)[base + i];
+                v[u] = ((const Pack *)x)[base + i];
+                if (RES) r[u] = ((const Pack *)res)[base + i];
             }
         }
 #pragma unroll
         for (int u = 0; u < BN_UNR; ++u) {
             const unsigned i = i0 + u * 256;
             if (i >= hw_vec) continue;
-            float4 o;
-            o.x = fmaf(v[u].x - mean, scale, shift) + (RES ? r[u].x : 0.f);
-            o.y = fmaf(v[u].y - mean, scale, shift) + (RES ? r[u].y : 0.f);
-            o.z = fmaf(v[u].z - mean, scale, shift) + (RES ? r[u].z : 0.f);
-            o.w = fmaf(v[u].w - mean, scale, shift) + (RES ? r[u].w : 0.f);
-            if (RELU) { o.x = relu_keep_nan(o.x); o.y = relu_keep_nan(o.y); o.z = relu_keep_nan(o.z); o.w = relu_keep_nan(o.w); }
-            ((float4 *)x)[base + i] = o;
+            Pack o;
+#pragma unroll
+            for (int e = 0; e < N; ++e)
+                bn_store(o.e[e], bn_elem<RES, RELU>(bn_load(v[u].e[e]), RES ? bn_load(r[u].e[e]) : 0.0f, mean, scale, shift));
+            ((Pack *)x)[base + i] = o;
         }
     } else {
 #pragma unroll
         for (int u = 0; u < BN_UNR; ++u) {
             const unsigned i = i0 + u * 256;
             if (i >= hw_vec) continue;
-            const float o = fmaf(x[base + i] - mean, scale, shift) + (RES ? res[base + i] : 0.0f);
-            x[base + i] = RELU ? relu_keep_nan(o) : o;
+            bn_store(x[base + i], bn_elem<RES, RELU>(bn_load(x[base + i]), RES ? bn_load(res[base + i]) : 0.0f, mean, scale, shift));
         }
     }
 }
 
-template <int VEC>
-static void launch_bn_act(float *x, const float *res, int64_t planes, unsigned hw_vec, unsigned C, const BnArgs &a,
+template <typename T, bool VECTOR>
+static void launch_bn_act(T *x, const T *res, int64_t planes, unsigned hw_vec, unsigned C, const BnArgs &a,
                           bool relu, hipStream_t s)
 {
     const unsigned gx = (unsigned)ceil_div((int64_t)hw_vec, (int64_t)(256 * BN_UNR));
     for (int64_t p0 = 0; p0 < planes; p0 += 65535) {
         const unsigned gy = (unsigned)((planes - p0) < 65535 ? (planes - p0) : 65535);
         const dim3 grid(gx, gy);
-        if (res && relu) hipLaunchKernelGGL((bn_act_kernel<VEC, true, true>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
-        else if (res)    hipLaunchKernelGGL((bn_act_kernel<VEC, true, false>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
-        else if (relu)   hipLaunchKernelGGL((bn_act_kernel<VEC, false, true>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
-        else             hipLaunchKernelGGL((bn_act_kernel<VEC, false, false>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
+        if (res && relu) hipLaunchKernelGGL((bn_act_kernel<T, VECTOR, true, true>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
+        else if (res)    hipLaunchKernelGGL((bn_act_kernel<T, VECTOR, true, false>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
+        else if (relu)   hipLaunchKernelGGL((bn_act_kernel<T, VECTOR, false, true>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
+        else             hipLaunchKernelGGL((bn_act_kernel<T, VECTOR, false, false>), grid, dim3(256), 0, s, x, res, p0, hw_vec, C, a);
     }
+}
+
+// the entry points: `who` names the one that was called
+template <typename T>
+static int bn_act(const char *who, T *x, const T *residual, int64_t N, int64_t C, int64_t HW, const float *mean, const float *var,
+                  const float *weight, const float *bias, float eps, int relu, void *stream)
+{
+    constexpr int64_t VEC = 16 / sizeof(T);
+    MDX_CHECK_ARG(x, "%s: NULL x", who);
+    MDX_CHECK_ARG((mean == nullptr) == (var == nullptr), "%s: mean and var must both be given or both be NULL", who);
+    MDX_CHECK_ARG(N > 0 && C > 0 && HW > 0, "%s: N=%lld C=%lld HW=%lld must be positive", who, (long long)N,
+                  (long long)C, (long long)HW);
+    MDX_CHECK_ARG(C < (1ll << 31) && HW < (1ll << 31), "%s: C or HW too large", who);
+    MDX_CHECK_ARG(eps >= 0.0f, "%s: eps=%g must be >= 0", who, (double)eps);
+    const BnArgs a{mean, var, weight, bias, eps};
+    const bool vec = (HW % VEC == 0) && (((uintptr_t)x & 15) == 0) && (!residual || ((uintptr_t)residual & 15) == 0);
+    if (vec) launch_bn_act<T, true>(x, residual, N * C, (unsigned)(HW / VEC), (unsigned)C, a, relu != 0, (hipStream_t)stream);
+    else     launch_bn_act<T, false>(x, residual, N * C, (unsigned)HW, (unsigned)C, a, relu != 0, (hipStream_t)stream);
+    MDX_LAUNCH_CHECK();
+    return MDX_OK;
 }
 
 }  // namespace mdx
@@ -99,18 +135,14 @@ extern "C" int mdx_bn_act(float *x, const float *residual, int64_t N, int64_t C,
                           const float *var, const float *weight, const float *bias, float eps, int relu,
                           void *stream)
 {
-    MDX_CHECK_ARG(x, "mdx_bn_act: NULL x");
-    MDX_CHECK_ARG((mean == nullptr) == (var == nullptr), "mdx_bn_act: mean and var must both be given or both be NULL");
-    MDX_CHECK_ARG(N > 0 && C > 0 && HW > 0, "mdx_bn_act: N=%lld C=%lld HW=%lld must be positive", (long long)N,
-                  (long long)C, (long long)HW);
-    MDX_CHECK_ARG(C < (1ll << 31) && HW < (1ll << 31), "mdx_bn_act: C or HW too large");
-    MDX_CHECK_ARG(eps >= 0.0f, "mdx_bn_act: eps=%g must be >= 0", (double)eps);
-    const BnArgs a{mean, var, weight, bias, eps};
-    const bool vec = (HW % 4 == 0) && (((uintptr_t)x & 15) == 0) && (!residual || ((uintptr_t)residual & 15) == 0);
-    if (vec) launch_bn_act<4>(x, residual, N * C, (unsigned)(HW / 4), (unsigned)C, a, relu != 0, (hipStream_t)stream);
-    else     launch_bn_act<1>(x, residual, N * C, (unsigned)HW, (unsigned)C, a, relu != 0, (hipStream_t)stream);
-    MDX_LAUNCH_CHECK();
-    return MDX_OK;
+    return bn_act<float>("mdx_bn_act", x, residual, N, C, HW, mean, var, weight, bias, eps, relu, stream);
+}
+
+extern "C" int mdx_bn_act_f16(__half *x, const __half *residual, int64_t N, int64_t C, int64_t HW, const float *mean,
+                              const float *var, const float *weight, const float *bias, float eps, int relu,
+                              void *stream)
+{
+    return bn_act<__half>("mdx_bn_act_f16", x, residual, N, C, HW, mean, var, weight, bias, eps, relu, stream);
 }
 
 // ---------------------------------------------------------------------------

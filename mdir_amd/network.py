@@ -19,7 +19,8 @@ from .wrapper import initialize_wrappers
 
 
 def init_cirnet(**params):
-    """``mdir/components/model/network/cirnet.py:10-22`` minus the model-zoo download."""
+    """``mdir/components/model/network/cirnet.py:10-22`` minus the model-zoo download.  ``precision`` ("f32" / "f16", optional)
+    passes through to ``init_network``."""
     for key in ["local_whitening", "pooling", "regional", "whitening", "pretrained"]:
         if key not in params:
             raise ValueError("Key '%s' not in params" % key)
@@ -53,11 +54,13 @@ class SingleNetwork:
         else:
             self.wrappers = {x: initialize_wrappers(wrappers, device) for x in ["train", "eval"]}
         self.frozen = network_params.runtime.get("frozen", False) or frozen
+        if "precision" in network_params.runtime:          # scenarios/eval_f16_trunk.yml: the labelled fp16 trunk of networks.py
+            model.set_precision(network_params.runtime["precision"])
         self.model = model.to(device)
         self.stage = None
         if self.frozen:
             self.eval()
-        extra = network_params.runtime.keys() - {"data", "wrappers", "frozen"}
+        extra = network_params.runtime.keys() - {"data", "wrappers", "frozen", "precision"}
         assert not extra, extra
         extra = network_params.runtime.get("data", {}).keys() - {"mean_std", "transforms"}
         assert not extra, extra

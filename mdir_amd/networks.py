@@ -13,6 +13,9 @@ MI355X-motivated and result-preserving:
   weight (re-tiled once), not a per-image mat-vec through torch;
 * nothing is ever downloaded: ``pretrained`` only loads files that already exist
   under ``model_dir`` / ``$CIRTORCH_ROOT/data``.
+
+``precision: f16`` (``init_network``) is a LABELLED mode, off by default: the input of ``features`` is cast to fp16, the feature
+maps stay fp16 up to the pooling, whose accumulator and everything after it are fp32 as always.  fp32 is the parity contract.
 """
 import os
 import pickle
@@ -22,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .backbones import OUTPUT_DIM, TrunkSequential, build_features
+from .backbones import OUTPUT_DIM, TrunkSequential, build_features, check_precision
 from .datasets import ImagesFromList, ToUint8HWC, device_convert, get_data_root, make_loader
 from .graphs import ShapeGraphs, graphs_enabled, parallel_map
 from .layers import POOLING, L2N, Rpool, pool_kind
@@ -52,9 +55,21 @@ class ImageRetrievalNet(nn.Module):
             self._whiten_index = (key, ops.DescriptorIndex(w.detach().contiguous(), "ND"))
         return self._whiten_index[1]
 
+    def set_precision(self, precision):
+        """"f32" or "f16" (module docstring): recorded in ``meta``; no parameter changes dtype."""
+        self.meta["precision"] = check_precision(self.meta["architecture"], precision)
+        return self
+
+    def trunk(self, x):
+        """``features(x)``; in the f16 mode on an fp16 copy of ``x``, and the maps come back fp16."""
+        if self.meta.get("precision", "f32") == "f16" and x.dtype == torch.float32:
+            x = x.half()
+        return self.features(x)
+
     def forward(self, x):
-        o = self.features(x)
+        o = self.trunk(x)
         if self.lwhiten is not None:   # local whitening: plain torch, not on the eval.py path
+            o = o.float()              # (an extra the f16 mode leaves alone: it gets fp32 maps)
             s = o.size()
             o = o.permute(0, 2, 3, 1).contiguous().view(-1, s[1])
             o = self.lwhiten(o)
@@ -62,8 +77,8 @@ class ImageRetrievalNet(nn.Module):
         kind = pool_kind(self.pool)
         if kind is not None:           # fused pool + L2N: mdx_pool_l2n
             o = ops.pool_l2n(o.contiguous(), kind[0], kind[1], kind[2], l2n_eps=self.norm.eps)
-        else:
-            o = self.norm(self.pool(o)).squeeze(-1).squeeze(-1)
+        else:                          # R-MAC, regional pooling: fp32 maps in either mode
+            o = self.norm(self.pool(o.float())).squeeze(-1).squeeze(-1)
         if self.whiten is not None:    # W o + b, then L2N: mdx_scores on the weight shard + mdx_l2n_rows
             y = self._whiten_shard().scores(o.contiguous(), "ND")
             bias = self.whiten.bias.detach() if self.whiten.bias is not None else None
@@ -80,8 +95,8 @@ class ImageRetrievalNet(nn.Module):
 
     def meta_repr(self):
         lines = ["  (meta): dict( "]
-        for key in ("architecture", "local_whitening", "pooling", "regional", "whitening"):
-            lines.append("     {}: {}".format(key, self.meta[key]))
+        for key in ("architecture", "local_whitening", "pooling", "regional", "whitening", "precision"):
+            lines.append("     {}: {}".format(key, self.meta.get(key, "f32") if key == "precision" else self.meta[key]))
         lines.append("     outputdim: {}".format(self.meta.get("out_channels", self.meta.get("outputdim"))))
         if "mean" in self.meta and "std" in self.meta:
             lines += ["     mean: {}".format(self.meta["mean"]), "     std: {}".format(self.meta["std"])]
@@ -104,7 +119,8 @@ def _local_file(url_or_path, directory):
 def init_network(params):
     """Build an ``ImageRetrievalNet`` from the reference's parameter dict
     (architecture, local_whitening, pooling, regional, whitening, mean, std,
-    pretrained, model_dir).  ``regional: True`` wraps the pooling into ``Rpool`` with a regional whitening
+    pretrained, model_dir; and ``precision``: "f32", the default, or "f16", the labelled half-precision trunk of the module
+    docstring -- resnet*, vgg*, alexnet).  ``regional: True`` wraps the pooling into ``Rpool`` with a regional whitening
     ``nn.Linear(dim, dim)`` (imageretrievalnet.py:205-222; its pre-computed weights are a download upstream: random here unless
     a checkpoint's state dict fills ``pool.whiten.*``)."""
     architecture = params.get("architecture", "resnet101")
@@ -119,6 +135,7 @@ def init_network(params):
 
     if architecture not in OUTPUT_DIM:
         raise ValueError("Unsupported or unknown architecture: {}!".format(architecture))
+    precision = check_precision(architecture, params.get("precision", "f32"))
     if pooling not in POOLING:
         raise KeyError("pooling '%s' is not one of %s" % (pooling, sorted(POOLING)))
     dim = OUTPUT_DIM[architecture]
@@ -139,7 +156,7 @@ def init_network(params):
             whiten.load_state_dict({"weight": P, "bias": -torch.mm(P, m).squeeze()})
 
     meta = {"architecture": architecture, "local_whitening": local_whitening, "pooling": pooling,
-            "regional": regional, "whitening": whitening, "mean": mean, "std": std, "outputdim": dim}
+            "regional": regional, "whitening": whitening, "mean": mean, "std": std, "outputdim": dim, "precision": precision}
     net = ImageRetrievalNet(features, lwhiten, pool, whiten, meta)
 
     if pretrained:
@@ -183,7 +200,8 @@ def extract_ms(net, input, ms, msp):
                    for s in ms]
     spec = net.fusable_tail() if hasattr(net, "fusable_tail") and os.environ.get("MDIR_AMD_FUSED_TAIL", "1") != "0" else None
     if spec is not None and 2 <= len(pyramid) <= 8:    # the whole tail in two launches, bit-identical to the route below
-        feats = parallel_map(lambda x: net.features(x).contiguous(), pyramid)
+        trunk = net.trunk if hasattr(net, "trunk") else net.features
+        feats = parallel_map(lambda x: trunk(x).contiguous(), pyramid)                # fp16 maps of an f16 net go in as they are
         out = ops.l2n_aggregate(ops.pool_multi(feats, *spec), net.norm.eps, msp)
         return out if input.shape[0] > 1 else out.reshape(-1)
     per_scale = parallel_map(lambda x: _rows(net, x).contiguous(), pyramid)           # one stream per scale
@@ -386,13 +404,13 @@ def extract_vectors(net, images, image_size, transform, bbxs=None, ms=[1], msp=1
 
 def extract_ssr(net, input):
     """The regional vectors of one image, ``[D, R]`` on the host (imageretrievalnet.py:354-355): ``Rpool`` without aggregation."""
-    return net.pool(net.features(input), aggregate=False).squeeze(0).squeeze(-1).squeeze(-1).permute(1, 0).cpu().data
+    return net.pool(net.trunk(input).float(), aggregate=False).squeeze(0).squeeze(-1).squeeze(-1).permute(1, 0).cpu().data
 
 
 def extract_ssl(net, input):
     """The local descriptors of one image, ``[D, H*W]`` on the host (imageretrievalnet.py:383-384): every location of the feature
     map L2-normalised over the channels (``net.norm`` on the map) -- one row per location through ``mdx_l2n_rows``."""
-    feat = net.features(input)
+    feat = net.trunk(input).float()
     c = feat.shape[1]
     rows = feat.squeeze(0).reshape(c, -1).t().contiguous()              # [H*W, C]
     return ops.l2n_rows_(rows, eps=net.norm.eps).t().contiguous().cpu().data

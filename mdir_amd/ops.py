@@ -96,16 +96,18 @@ def _workspace(nbytes, device):
 def pool_l2n(feat, kind="gem", p=3.0, pool_eps=1e-6, l2n_eps=1e-6):
     """[B,C,H,W] feature maps -> [B,C] pooled (+ L2-normalised unless l2n_eps is None).
 
-    ``self.norm(self.pool(o))`` of cirtorch/networks/imageretrievalnet.py:108."""
+    ``self.norm(self.pool(o))`` of cirtorch/networks/imageretrievalnet.py:108.  fp16 maps (the ``precision: f16`` trunk) go to
+    ``mdx_pool_l2n_f16``: fp32 out, the bits of the fp32 call on ``feat.float()``."""
     if feat.dim() != 4:
         raise ValueError("feature map must be [B,C,H,W]")
-    fp = _dev(feat, torch.float32, "feature map")
+    half = isinstance(feat, torch.Tensor) and feat.dtype == torch.float16
+    fp = _dev(feat, torch.float16 if half else torch.float32, "feature map")
     B, C, H, W = feat.shape
     out = torch.empty((B, C), dtype=torch.float32, device=feat.device)
+    fn, name = (_lib.lib().mdx_pool_l2n_f16, "mdx_pool_l2n_f16") if half else (_lib.lib().mdx_pool_l2n, "mdx_pool_l2n")
     with _on(feat):
-        check(_lib.lib().mdx_pool_l2n(fp, B, C, H, W, POOL_KINDS[kind], float(p), float(pool_eps),
-                                      -1.0 if l2n_eps is None else float(l2n_eps), _vp(out.data_ptr()),
-                                      _stream()), "mdx_pool_l2n")
+        check(fn(fp, B, C, H, W, POOL_KINDS[kind], float(p), float(pool_eps), -1.0 if l2n_eps is None else float(l2n_eps),
+                 _vp(out.data_ptr()), _stream()), name)
     return out
 
 
@@ -212,24 +214,28 @@ def ms_aggregate_batch(mats, msp=1.0):
 
 def pool_multi(feats, kind="gem", p=3.0, pool_eps=1e-6):
     """The feature maps of one pyramid (list of ``[B,C,H_s,W_s]``, same B and C) -> pooled ``[S,B,C]`` in ONE launch
-    (``mdx_pool_multi``); no normalisation."""
+    (``mdx_pool_multi``); no normalisation.  All fp32, or all fp16 (``mdx_pool_multi_f16``: fp32 out, the bits of the fp32
+    call on the maps' ``.float()``); mixed maps are refused."""
     if not 1 <= len(feats) <= 8:
         raise ValueError("1..8 scales supported, got %d" % len(feats))
     if feats[0].dim() != 4:
         raise ValueError("feature maps must be [B,C,H,W]")
     B, C = feats[0].shape[:2]
     S = len(feats)
+    half = feats[0].dtype == torch.float16
+    if any(f.dtype != feats[0].dtype for f in feats):
+        raise ValueError("the maps of one pool_multi call must share a dtype, got %s" % [str(f.dtype) for f in feats])
     ptrs = (ctypes.c_void_p * S)()
     hs, ws = (ctypes.c_int * S)(), (ctypes.c_int * S)()
     for i, f in enumerate(feats):
         if f.dim() != 4 or tuple(f.shape[:2]) != (B, C):
             raise ValueError("map %d is %s, expected [%d,%d,H,W]" % (i, tuple(f.shape), B, C))
-        ptrs[i] = _dev(f, torch.float32, "feature map").value
+        ptrs[i] = _dev(f, torch.float16 if half else torch.float32, "feature map").value
         hs[i], ws[i] = f.shape[2], f.shape[3]
     out = torch.empty((S, B, C), dtype=torch.float32, device=feats[0].device)
+    fn, name = (_lib.lib().mdx_pool_multi_f16, "mdx_pool_multi_f16") if half else (_lib.lib().mdx_pool_multi, "mdx_pool_multi")
     with _on(feats[0]):
-        check(_lib.lib().mdx_pool_multi(ptrs, S, B, C, hs, ws, POOL_KINDS[kind], float(p), float(pool_eps),
-                                        _vp(out.data_ptr()), _stream()), "mdx_pool_multi")
+        check(fn(ptrs, S, B, C, hs, ws, POOL_KINDS[kind], float(p), float(pool_eps), _vp(out.data_ptr()), _stream()), name)
     return out
 
 
@@ -337,9 +343,11 @@ def resample_u8(images, axis, bounds, taps):
 def bn_act_(x, running_mean, running_var, weight=None, bias=None, eps=1e-5, residual=None, relu=True):
     """In place on a convolution output ``x [N,C,H,W]``: inference batch-norm, ``+ residual``, ReLU
     in one pass (``mdx_bn_act``); returns ``x``.  Called ~100 times per image by a launch-bound trunk,
-    so the checks are kept to what protects the raw pointers."""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
-        raise ValueError("bn_act_ expects a contiguous fp32 [N,C,H,W] CUDA/ROCm tensor (no CPU fallback)")
+    so the checks are kept to what protects the raw pointers.  An fp16 ``x`` (with an fp16 residual; the statistics stay fp32)
+    goes to ``mdx_bn_act_f16``: the same fp32 arithmetic on the upcast elements, rounded once to fp16."""
+    half = x.dtype == torch.float16
+    if not (x.is_cuda and (half or x.dtype == torch.float32) and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("bn_act_ expects a contiguous fp32 (or fp16) [N,C,H,W] CUDA/ROCm tensor (no CPU fallback)")
     n, c, h, w = x.shape
     ptrs = []
     for name, t in (("running_mean", running_mean), ("running_var", running_var), ("weight", weight), ("bias", bias)):
@@ -353,15 +361,15 @@ def bn_act_(x, running_mean, running_var, weight=None, bias=None, eps=1e-5, resi
         raise ValueError("running_mean and running_var must both be given or both be None")
     rp = None
     if residual is not None:
-        if residual.shape != x.shape or residual.dtype != torch.float32 or residual.device != x.device \
+        if residual.shape != x.shape or residual.dtype != x.dtype or residual.device != x.device \
                 or not residual.is_contiguous():
-            raise ValueError("residual must be contiguous fp32 and shaped like x")
+            raise ValueError("residual must be contiguous %s and shaped like x" % ("fp16" if half else "fp32"))
         rp = residual.data_ptr()
     if x.numel() == 0:
         return x
+    fn, name = (_lib.lib().mdx_bn_act_f16, "mdx_bn_act_f16") if half else (_lib.lib().mdx_bn_act, "mdx_bn_act")
     with _on(x):
-        check(_lib.lib().mdx_bn_act(x.data_ptr(), rp, n, c, h * w, ptrs[0], ptrs[1], ptrs[2], ptrs[3], float(eps),
-                                    1 if relu else 0, _stream()), "mdx_bn_act")
+        check(fn(x.data_ptr(), rp, n, c, h * w, ptrs[0], ptrs[1], ptrs[2], ptrs[3], float(eps), 1 if relu else 0, _stream()), name)
     return x
 
 

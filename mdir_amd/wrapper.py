@@ -149,7 +149,8 @@ class CirMultiscaleAggregation(Wrapper):
         if spec is None or waslist or len(self.scales) < 2 or len(pyramid) != len(self.scales) \
                 or os.environ.get("MDIR_AMD_FUSED_TAIL", "1") == "0":
             return None
-        feats = parallel_map(lambda x: model.features(x.to(device)).contiguous(), pyramid)
+        trunk = model.trunk if hasattr(model, "trunk") else model.features               # (an f16 net casts there)
+        feats = parallel_map(lambda x: trunk(x.to(device)).contiguous(), pyramid)
         out = ops.l2n_aggregate(ops.pool_multi(feats, *spec), model.norm.eps, self._msp(model))
         return out if out.shape[0] > 1 else out.reshape(-1)
 

@@ -9,7 +9,11 @@ descriptor tail (mdx_pool_l2n, mdx_ms_aggregate, mdx_scores(P)+mdx_l2n_rows), me
 events on the current stream, and the same tail expressed with stock torch ops (the reference's
 LF.gem / LF.l2n / aggregate_tensor / CirtorchWhiten.postprocess statements) for comparison.
 
-    python tools/bench_extract.py [--arch resnet101] [--images 30] [--fp16-backbone]
+    python tools/bench_extract.py [--arch resnet101] [--images 30] [--precision f16] [--accuracy 32]
+
+``--precision f16``: the labelled half-precision trunk (``init_network`` ``precision``): fp16 maps, ``mdx_bn_act_f16``, the tail
+pooled from fp16 into fp32.  ``--accuracy N`` adds the distance of the f16 descriptors of N random images from the fp32 ones of the
+same network (max-abs, cosine distance, top-10 slot agreement of a query-equals-database ranking).
 """
 import argparse
 import json
@@ -31,18 +35,22 @@ def main():
     ap.add_argument("--no-graphs", action="store_true", help="eager launches instead of one hipGraph replay per image")
     ap.add_argument("--batch", type=int, default=4, help="equal-sized images per trunk pass (1 = the reference's batch size)")
     ap.add_argument("--miopen-find", action="store_true", help="torch.backends.cudnn.benchmark = True (MIOpen find mode)")
+    ap.add_argument("--precision", choices=("f32", "f16"), default="f32", help="f16: the labelled half-precision trunk (default: f32)")
+    ap.add_argument("--accuracy", type=int, default=0, metavar="N", help="also report f16 against fp32 descriptors of N random images")
     print(json.dumps(measure(ap.parse_args())))
 
 
 def measure(args):
-    """``args``: namespace with arch / images / channels_last / miopen_find (also called by bench.py)."""
+    """``args``: namespace with arch / images / channels_last / miopen_find (also called by bench.py); optional ``precision``
+    ("f32") and ``accuracy`` (0)."""
     from mdir_amd import ops
     from mdir_amd.networks import init_network
     from mdir_amd.wrapper import initialize_wrappers
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.backends.cudnn.benchmark = bool(args.miopen_find)
     torch.manual_seed(3)
-    net = init_network({"architecture": args.arch, "pooling": "gem", "whitening": False, "pretrained": False})
+    precision = getattr(args, "precision", "f32")
+    net = init_network({"architecture": args.arch, "pooling": "gem", "whitening": False, "pretrained": False, "precision": precision})
     net.meta["in_channels"], net.meta["out_channels"] = 3, net.meta["outputdim"]
     net = net.to(dev).eval()
     if args.channels_last:
@@ -90,7 +98,7 @@ def measure(args):
         # split: features only / tail only (on precomputed feature maps)
         pyr = [F.interpolate(imgs[0], scale_factor=s, mode="bilinear", align_corners=False) if s != 1 else imgs[0]
                for s in chain.wrappers[1].scales]
-        feats = [net.features(x).contiguous() for x in pyr]
+        feats = [net.trunk(x).contiguous() for x in pyr]
         ev = lambda: torch.cuda.Event(enable_timing=True)
         reps = 20
 
@@ -103,8 +111,8 @@ def measure(args):
             b.record(); torch.cuda.synchronize()
             return a.elapsed_time(b) / reps
 
-        t_backbone_eager = timeit(lambda: [net.features(x) for x in pyr])
-        trunk = ShapeGraphs(lambda x: [net.features(p) for p in
+        t_backbone_eager = timeit(lambda: [net.trunk(x) for x in pyr])
+        trunk = ShapeGraphs(lambda x: [net.trunk(p) for p in
                                        [x] + [F.interpolate(x, scale_factor=s, mode="bilinear", align_corners=False)
                                               for s in chain.wrappers[1].scales if s != 1]], warmup=1)
         trunk(imgs[0]); trunk(imgs[0])
@@ -125,6 +133,7 @@ def measure(args):
         def tail_torch():   # the reference's statements with stock torch ops
             per = []
             for f in feats:
+                f = f.float()
                 o = F.avg_pool2d(f.clamp(min=1e-6).pow(p), (f.size(-2), f.size(-1))).pow(1. / p)
                 per.append((o / (torch.norm(o, p=2, dim=1, keepdim=True) + 1e-6)).squeeze(-1).squeeze(-1).permute(1, 0))
             v = torch.zeros(D, device=dev)
@@ -147,7 +156,8 @@ def measure(args):
         t_tail_replay = (timeit(lambda: tail_graph(dummy)) if tail_graph.graphs else t_tail_eager) + timeit(tail_whiten_all) / args.images
         t_tail = t_tail_eager
         t_tail_torch = timeit(tail_torch)
-        tail_bytes = sum(4.0 * f.numel() for f in feats) + 4.0 * (len(feats) + 3) * D           # maps read once + the vectors
+        tail_bytes = sum(float(f.element_size()) * f.numel() for f in feats) + 4.0 * (len(feats) + 3) * D   # maps read once + the vectors
+        accuracy = _f16_accuracy(net, chain, getattr(args, "accuracy", 0), bmax, dev) if precision == "f16" and getattr(args, "accuracy", 0) else None
     return {"metric": "descriptors/sec, %s-GeM, 3 scales of 1024x768 + whitening, 1 GPU" % args.arch,
             "value": round(args.images / total, 2), "unit": "descriptors/s",
             "ms_per_image": round(1e3 * total / args.images, 3),
@@ -159,8 +169,32 @@ def measure(args):
                               "what": "GeM of the three maps (one launch), their L2Ns + the aggregation (one launch), whitening of the "
                                       "finished [N,D] matrix / N: two short dependent launches per image (or per batch of 8), so launch "
                                       "latency, not bandwidth, bounds it"},
-            "tail_max_abs_diff_vs_torch_ops": err, "dtype": "f32", "data": "synthetic",
-            "hipgraph_replays": getattr(describe, "replays", 0)}
+            "tail_max_abs_diff_vs_torch_ops": err, "dtype": precision, "data": "synthetic",
+            "hipgraph_replays": getattr(describe, "replays", 0),
+            **({"f16_against_f32": accuracy} if accuracy else {})}
+
+
+def _f16_accuracy(net, chain, n, batch, dev):
+    """The whitened descriptors of ``n`` random 1024x768 images from the f16 trunk against those of the SAME network run in fp32
+    (``set_precision``): max-abs and cosine distance, and in how many of the top-10 slots of a query-equals-database ranking
+    the two name the same image (as tests/test_gpu_f16.py reports for the fp16 shard)."""
+    g = torch.Generator().manual_seed(17)
+    n = -(-n // batch) * batch
+    rows = {}
+    for precision in ("f32", "f16"):
+        net.set_precision(precision)
+        out = []
+        for i in range(0, n, batch):
+            g.manual_seed(17 + i)
+            out.append(chain(torch.randn(batch, 3, 768, 1024, generator=g).to(dev), net).reshape(batch, -1).clone())
+        rows[precision] = torch.cat(out)
+    a, b = rows["f32"], rows["f16"]
+    k = min(10, n)
+    top = lambda x: (x @ x.t()).topk(k, dim=1).indices
+    return {"images": n, "max_abs": float((a - b).abs().max()), "max_cosine_distance": float((1 - (a * b).sum(dim=1)).max()),
+            "top10_slot_agreement": float((top(a) == top(b)).float().mean()),
+            "what": "random-weight trunk on gaussian noise images: the descriptors of different images are far closer to each other "
+                    "than those of photographs, so the ranking agreement is a harsh reading"}
 
 
 # rOxford-like sizes (W, H): longer side 1024 after the thumbnail, the usual camera aspect ratios, both orientations
@@ -202,13 +236,14 @@ def _conv_flops(net, scales, h, w):
     return float(total[0])
 
 
-def measure_list(arch="resnet101", workers=8, short=12, mid=40, long=64):
+def measure_list(arch="resnet101", workers=8, short=12, mid=40, long=64, precision="f32"):
     """Descriptors/sec of ``extract_vectors_device`` on an image LIST: 16 sizes, JPEG files through the real loader
     (decode + thumbnail in worker processes, uint8 over PCIe, /255-mean-std on the GPU), 3 scales + learned whitening
     through the wrapper chain.  The FIRST list of the process (``short`` images per size: 12 = one batch of eight + one of
     four, the two batch shapes extraction uses) pays for what a new size costs (MIOpen picks and loads its kernels for every
     (size, scale, batch)); two later lists (``mid`` / ``long`` per size, both long enough for a graph per
-    size: one eager batch, one capture, replays) differ only in replays, which gives the steady state."""
+    size: one eager batch, one capture, replays) differ only in replays, which gives the steady state.
+    ``precision``: "f32", or "f16" for the labelled half-precision trunk."""
     import tempfile
     from mdir_amd.datasets import ImagesFromList, initialize_transforms
     from mdir_amd.graphs import ShapeGraphs
@@ -220,7 +255,7 @@ def measure_list(arch="resnet101", workers=8, short=12, mid=40, long=64):
     from mdir_amd.networks import extract_vectors_device, init_network
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(3)
-    model = init_network({"architecture": arch, "pooling": "gem", "whitening": False, "pretrained": False})
+    model = init_network({"architecture": arch, "pooling": "gem", "whitening": False, "pretrained": False, "precision": precision})
     D = model.meta["outputdim"]
     model.meta["in_channels"], model.meta["out_channels"] = 3, D
     rng = np.random.default_rng(2)
@@ -262,6 +297,8 @@ def measure_list(arch="resnet101", workers=8, short=12, mid=40, long=64):
     steady = (times["warm_long"] - times["warm_mid"]) / (nl - nm)           # s per image once its size has a graph
     first = (times["cold"] - times["warm_short"]) / len(LIST_SHAPES)        # extra s per size the process has never seen
     flops = np.mean([_conv_flops(model, [1, 2 ** -0.5, 0.5], h, w) for w, h in LIST_SHAPES[:1] + LIST_SHAPES[4:5] + LIST_SHAPES[8:9]])
+    # the matrix-core peak the trunk is read against: fp32 MFMA, or the dense fp16 MFMA (~2.5 PFLOP/s, about 16 x) in the f16 mode
+    peak = 157.3 if precision == "f32" else 2500.0
     # the headline figure is a WHOLE list, start to finish, graph captures included (one wall-clock timing); the difference
     # of two such timings -- the steady state between captures -- swings with the box and is a derived estimate only
     return {"value": round(nl / times["warm_long"], 2), "unit": "descriptors/s",
@@ -284,13 +321,15 @@ def measure_list(arch="resnet101", workers=8, short=12, mid=40, long=64):
             # the extraction half's own roofline: the trunk's convolutions are the flops of an image (the hand-written tail is
             # `roofline_tail`, launch-bound).  Two readings: over the whole warm list (what `value` is) and at the steady state.
             "roofline": {"kernel": "trunk convolutions: MIOpen (owner of the kernels) + mdx::conv1x1_bn_act_kernel for the Bottleneck expand 1x1 "
-                                   "convolutions, mdx::bn_act_kernel epilogues; fp32",
-                         "bound": "mfma", "achieved": round(flops * nl / times["warm_long"] / 1e12, 2), "peak": 157.3, "unit": "TFLOP/s",
-                         "frac": round(flops * nl / times["warm_long"] / 1e12 / 157.3, 4),
-                         "achieved_at_steady_state": round(flops / steady / 1e12, 2), "frac_at_steady_state": round(flops / steady / 1e12 / 157.3, 4),
+                                   "convolutions, mdx::bn_act_kernel epilogues; fp32" if precision == "f32" else
+                                   "trunk convolutions: MIOpen on fp16 maps (all of them), mdx::bn_act_kernel<__half> epilogues; fp16 in, fp32 accumulation",
+                         "bound": "mfma", "achieved": round(flops * nl / times["warm_long"] / 1e12, 2), "peak": peak, "unit": "TFLOP/s",
+                         "frac": round(flops * nl / times["warm_long"] / 1e12 / peak, 4),
+                         "achieved_at_steady_state": round(flops / steady / 1e12, 2), "frac_at_steady_state": round(flops / steady / 1e12 / peak, 4),
                          "algorithmic_flops_per_image": flops, "traffic": None,
                          "what": "2 x multiply-adds of every convolution of the three scales (hooks on an eager pass, mean of three of the 16 sizes) "
                                  "x images / wall time of the whole warm list (loader, graph captures, tail and whitening included in the time)"},
+            **({} if precision == "f32" else {"precision": precision}),      # (the default's result keeps its fields as they were)
             "miopen_find_mode": os.environ.get("MIOPEN_FIND_MODE"),
             "graph_captures": __import__("mdir_amd.graphs", fromlist=["capture_stats"]).capture_stats()}
 
@@ -376,6 +415,6 @@ if __name__ == "__main__":
     elif len(sys.argv) > 1 and sys.argv[1] == "--cpu-loop":
         print(json.dumps(cpu_reference_loop(images=int(sys.argv[2]) if len(sys.argv) > 2 else 2)))
     elif len(sys.argv) > 1 and sys.argv[1] == "--list":
-        print(json.dumps(measure_list(*(sys.argv[2:3] or ["resnet101"]))))
+        print(json.dumps(measure_list(*(sys.argv[2:3] or ["resnet101"]), precision=(sys.argv[3:4] or ["f32"])[0])))   # --list ARCH [f32|f16]
     else:
         main()
