@@ -879,6 +879,65 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * here, the names into _lib.EXPORTS and the cases into the table, and delete the second header. */
 #include "mdx_knn_join.h"
 
+/* --------------------------------------------------------------- near-duplicate groups */
+
+/* The connected components of the exact self-join, at up to MDX_GROUPS_MAX_T = 8 thresholds from one pass over the candidates.
+ * For rows x_0 .. x_{n-1} (fp32, row-major) and a finite fp32 threshold tau, G_tau is the undirected graph with an edge i ~ j
+ * (i != j) iff chain(i, j) >= tau -- chain the exact score of "exact range search and self-join": bitwise symmetric, and a NaN score
+ * is never an edge.  Those are exactly the pairs the self-join reports.
+ *     label_tau[i] = min { j : j is connected to i in G_tau }        (i itself included)
+ * so labels[i] == i exactly for the representatives.  For T thresholds (1 <= T <= MDX_GROUPS_MAX_T, any order, duplicates allowed)
+ * the result is labels int64 [T, n], row t for taus[t].  The labels depend on the inputs only: not on chunking, buffer sizes, launch
+ * order, the route (candidates of the int8 join kernel, or dense fp32 scores), or which candidates were skipped.  Rows with NaN or
+ * infinite values, all-zero rows and subnormal rows are handled as the self-join handles them: the candidates are the join
+ * kernel's (its proofs apply unchanged) and the chain that decides them is the same.
+ *
+ * Forest.  parent int32 [T, n] (so n < 2^31), one forest per threshold.  parent[x] <= x at all times; a root has parent[x] == x.
+ *   find(x) follows parents; it may halve the path, which only ever lowers parent[x] to an ancestor of x.  unite(a, b) loops:
+ *   ra = find(a), rb = find(b); done if equal; hi = max, lo = min; compare-and-swap(parent[hi]: hi -> lo); done if it succeeded,
+ *   else go on from the value it returned.  Only a root is ever hooked, and always under a smaller id, so the root of every tree is
+ *   its minimum, and once every edge is in each component is one tree whose root is the label.  (A hook by an atomic min on a
+ *   non-root can drop a link, and is not used.)
+ * Memory model.  On this chip a CU's L1 is never refreshed by another CU's stores and the L2s of the XCDs are not coherent with
+ *   each other for plain accesses.  Inside a kernel that also writes parent, every read of parent is an agent-scope relaxed atomic
+ *   load and every write an agent-scope atomic; after a failed compare-and-swap the loop continues from the returned value and never
+ *   from a fresh plain load -- which could return the same stale "I am a root" for ever against a compare-and-swap that sees the
+ *   truth.  Stale values are harmless otherwise: an old parent is still an ancestor.  The label pass is a launch of its own behind
+ *   the unions and reads with plain loads.
+ * Bounded loops.  A find takes at most n steps; a unite retries only after another thread hooked the same root, and a level has
+ *   at most n - 1 hooks.  Both loops count, and beyond n + 1 they set bit 0 of the flags and return without hooking.  Nothing
+ *   waits on another workgroup: no flags, no grid barriers, no spins.
+ * Skip rule (mdx_groups_union_pairs).  Before a pair is staged, if find(i) == find(j) in the level of the LARGEST threshold the
+ *   pair is dropped and its chain is never computed.  Sound: a path in that level consists of hooks, each made for a pair whose
+ *   chain reaches the largest threshold and so every threshold; the thread that computed such a chain unites its pair in EVERY
+ *   level before it ends (in this launch, or in an earlier one on the same stream).  So when the kernel ends i and j are connected
+ *   in every level, which is all the dropped pair could have added, whatever its own chain.  The components are unchanged; only
+ *   the counters of chains and edges depend on the schedule.
+ *
+ * Stages (all enqueue only, on the caller's stream; no workspace):
+ *   mdx_groups_init         parent[t][i] = i for T levels of n rows; status (device int64 [4]) = 0.
+ *   mdx_groups_union_pairs  pairs [P] = i << 32 | j as mdx_join_candidates (symmetric) writes them, in any order, duplicates
+ *                           allowed, of rows [n, d] at a stride of ld.  One workgroup per 64 pairs: the skip rule, then the exact
+ *                           chain of the rows of every pair left (the tile plan of the join's exact stage: k ascending from +0 over
+ *                           zeros to round_up(d, 64); 16-byte loads only when ld % 4 == 0 and rows is 16-byte aligned), then unite
+ *                           in every level t with chain >= taus[t].  taus: a HOST pointer to T floats (passed to the kernel by value).
+ *                           A pair with i == j is dropped; one that names a row >= n is dropped and sets bit 1 of the flags.
+ *   mdx_groups_union_dense  the exact route: scores fp32 [m, ncols] at a stride of ld (mdx_scores_rowmajor / mdx_scores output);
+ *                           entry (r, c) is the pair (row_base + r, col_base + c), an edge of level t iff s >= taus[t] and
+ *                           col_base + c > row_base + r.  One workgroup per row.
+ *   mdx_groups_labels       labels int64 [T, n] = the root of every row; labels is a buffer of its own, never parent.
+ * status: [0] chains computed, [1] pairs that were an edge of at least one level, [2] successful hooks summed over the levels,
+ *   [3] flags (bit 0: a loop gave up -- the labels are then not to be used; bit 1: a pair out of range).  One atomic add per
+ *   workgroup and word.  [0] and [1] vary from run to run under the skip rule (the dense route computes no chain and adds nothing
+ *   to [0]); [2] does not: it is the sum over t of n minus the number of groups of level t.
+ * MDX_ERR_INVALID, nothing launched, for a NULL pointer, n, d, P, m or ncols < 1, n or P at or above 2^31, T outside [1, 8], a
+ * non-finite threshold, ld below d (pairs) or below ncols (dense), a negative base, row_base + m > n or col_base + ncols > n,
+ * labels == parent. */
+/* The prototypes of this section (and MDX_GROUPS_MAX_T) are in mdx_groups.h, beside this file, and their names in
+ * _lib.GROUPS_EXPORTS, for the reason given above for mdx_knn_join.h; their census is tests/test_groups_host.py (every prototype is
+ * exported, bound, and has cases in tests/test_gpu_groups_memcontract.py). */
+#include "mdx_groups.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

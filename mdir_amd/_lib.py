@@ -36,7 +36,7 @@ ABI_VERSION = 3        # include/mdx.h MDX_ABI_VERSION this binding was written 
 def build(force=False):
     """Compile libmdx.so with hipcc --offload-arch=gfx950 (see csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h", "mdx_groups.h")]
     stale = not os.path.exists(LIB_PATH) or \
         any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -100,6 +100,10 @@ def _declare(lib):
         "mdx_join_candidates_rows": (i32, [p, p, p, p, i64, i64, p, p, i64, p, p]),
         "mdx_knn_resolve_workspace": (i64, [i64, i64]),
         "mdx_knn_resolve": (i32, [p, i64, p, i64, i64, p, i64, i64, i64, i64, p, p, p, p, i64, p]),
+        "mdx_groups_init": (i32, [p, i64, i64, p, p]),
+        "mdx_groups_union_pairs": (i32, [p, i64, i64, p, i64, ctypes.POINTER(ctypes.c_float), i64, p, i64, p, p]),
+        "mdx_groups_union_dense": (i32, [p, i64, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_float), i64, p, i64, p, p]),
+        "mdx_groups_labels": (i32, [p, i64, i64, p, p]),
         "mdx_bn_act_f16": (i32, [p, p, i64, i64, i64, p, p, p, p, f32, i32, p]),
         "mdx_pool_l2n_f16": (i32, [p, i32, i32, i32, i32, i32, f32, f32, f32, p, p]),
         "mdx_pool_multi_f16": (i32, [pp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32, f32, f32, p, p]),
@@ -181,6 +185,10 @@ KNN_JOIN_EXPORTS = ("mdx_knn_bounds_workspace", "mdx_knn_bounds", "mdx_join_cand
 # include/mdx_trunk_f16.h (included by mdx.h): the fp16 trunk mode, apart from EXPORTS for the same reason; the census of these is
 # tests/test_trunk_f16_host.py (include/mdx.h, "fp16 trunk")
 TRUNK_F16_EXPORTS = ("mdx_bn_act_f16", "mdx_pool_l2n_f16", "mdx_pool_multi_f16")
+
+# include/mdx_groups.h (included by mdx.h): the near-duplicate groups, apart from EXPORTS for the same reason; the census of these
+# is tests/test_groups_host.py (include/mdx.h, "near-duplicate groups")
+GROUPS_EXPORTS = ("mdx_groups_init", "mdx_groups_union_pairs", "mdx_groups_union_dense", "mdx_groups_labels")
 
 
 def lib():

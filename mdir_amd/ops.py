@@ -947,6 +947,103 @@ def knn_resolve(rows_a, rows_b, pairs, m_lo, m, k):
     return ids, scores, counts
 
 
+# ------------------------------------------------------------- near-duplicate groups
+
+GROUPS_MAX_T = 8                  # include/mdx.h MDX_GROUPS_MAX_T: thresholds (levels of the forest) of one pass
+GROUPS_GAVE_UP, GROUPS_OUT_OF_RANGE = 1, 2       # the flags of status[3]
+
+
+def _taus(thresholds):
+    """The thresholds of a groups call as a ctypes float array (the C ABI reads them on the host) and their number."""
+    if isinstance(thresholds, (bool, int, float)):
+        thresholds = [thresholds]
+    if not isinstance(thresholds, (list, tuple)) or not 1 <= len(thresholds) <= GROUPS_MAX_T:
+        raise ValueError("thresholds: a number or a sequence of 1 to GROUPS_MAX_T = %d numbers, got %r" % (GROUPS_MAX_T, thresholds))
+    vals = [_tau(t) for t in thresholds]
+    return (ctypes.c_float * len(vals))(*vals), len(vals)
+
+
+def _forest(parent, status):
+    """(parent pointer, status pointer, T, n) of a forest as :func:`groups_init` makes it."""
+    pp = _dev(parent, torch.int32, "parent")
+    sp = _dev(status, torch.int64, "status")
+    if parent.dim() != 2 or parent.shape[0] < 1 or parent.shape[0] > GROUPS_MAX_T or parent.shape[1] < 1:
+        raise ValueError("parent must be the int32 [T, n] forest of groups_init, got %s" % (tuple(parent.shape),))
+    if status.dim() != 1 or status.shape[0] != 4:
+        raise ValueError("status must be the int64 [4] words of groups_init, got %s" % (tuple(status.shape),))
+    return pp, sp, parent.shape[0], parent.shape[1]
+
+
+def groups_init(levels, n, device):
+    """``(parent int32 [levels, n], status int64 [4])``: a forest of singletons, ``parent[t, i] = i``, and zeroed counters
+    (``mdx_groups_init``, include/mdx.h "near-duplicate groups")."""
+    for name, v, hi in (("levels", levels, GROUPS_MAX_T), ("n", n, _MAX_ITEMS)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError("groups_init: %s must be an integer in [1, %d], got %r" % (name, hi, v))
+    parent = torch.empty((levels, n), dtype=torch.int32, device=device)
+    status = torch.empty(4, dtype=torch.int64, device=device)
+    with _on(parent):
+        check(_lib.lib().mdx_groups_init(_vp(parent.data_ptr()), levels, n, _vp(status.data_ptr()), _stream()), "mdx_groups_init")
+    return parent, status
+
+
+def groups_union_pairs(rows, pairs, thresholds, parent, status):
+    """Unites, in every level t of ``parent`` whose ``thresholds[t]`` the exact chain of the pair reaches, the two rows of each of
+    ``pairs`` (int64 ``i << 32 | j`` as :func:`join_candidates` writes them, any order, duplicates allowed) of ``rows`` fp32
+    ``[n, d]`` (``mdx_groups_union_pairs``).  Enqueues only."""
+    rp, ld = _rows(rows, "rows")
+    tv, T = _taus(thresholds)
+    pp, sp, levels, n = _forest(parent, status)
+    if levels != T or rows.shape[0] != n:
+        raise ValueError("groups_union_pairs: %d thresholds and %d rows for a forest of [%d, %d]" % (T, rows.shape[0], levels, n))
+    kp = _dev(pairs, torch.int64, "pairs")
+    P = pairs.numel()
+    if pairs.dim() != 1 or not 1 <= P <= _MAX_ITEMS:
+        raise ValueError("groups_union_pairs: pairs must be a 1-d tensor of 1 to 2^31 - 1 pairs, got %s" % (tuple(pairs.shape),))
+    with _on(rows):
+        check(_lib.lib().mdx_groups_union_pairs(rp, ld, rows.shape[1], kp, P, tv, T, pp, n, sp, _stream()), "mdx_groups_union_pairs")
+
+
+def groups_union_dense(scores, row_base, col_base, thresholds, parent, status):
+    """The same for a dense fp32 score block ``[m, ncols]`` (rows contiguous, any stride) whose entry (r, c) is the pair
+    ``(row_base + r, col_base + c)``: an edge of level t iff ``s >= thresholds[t]`` and the column's row id is the larger
+    (``mdx_groups_union_dense``).  Enqueues only."""
+    sp_, ld = _rows(scores, "scores")
+    tv, T = _taus(thresholds)
+    pp, sp, levels, n = _forest(parent, status)
+    m, ncols = scores.shape
+    for name, v in (("row_base", row_base), ("col_base", col_base)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError("groups_union_dense: %s must be an integer >= 0, got %r" % (name, v))
+    if levels != T or m < 1 or ncols < 1 or row_base + m > n or col_base + ncols > n:
+        raise ValueError("groups_union_dense: %d thresholds, rows [%d, +%d) x columns [%d, +%d) for a forest of [%d, %d]"
+                         % (T, row_base, m, col_base, ncols, levels, n))
+    with _on(scores):
+        check(_lib.lib().mdx_groups_union_dense(sp_, m, ncols, ld, row_base, col_base, tv, T, pp, n, sp, _stream()), "mdx_groups_union_dense")
+
+
+def groups_labels(parent):
+    """int64 ``[T, n]``: the label of every row in every level, the smallest id of its group (``mdx_groups_labels``); a buffer
+    of its own, ``parent`` is left as it is."""
+    pp = _dev(parent, torch.int32, "parent")
+    if parent.dim() != 2 or parent.shape[0] < 1 or parent.shape[0] > GROUPS_MAX_T or parent.shape[1] < 1:
+        raise ValueError("parent must be the int32 [T, n] forest of groups_init, got %s" % (tuple(parent.shape),))
+    T, n = parent.shape
+    labels = torch.empty((T, n), dtype=torch.int64, device=parent.device)
+    with _on(parent):
+        check(_lib.lib().mdx_groups_labels(pp, T, n, _vp(labels.data_ptr()), _stream()), "mdx_groups_labels")
+    return labels
+
+
+def groups_status(status):
+    """``{"chains", "edges", "hooks", "flags"}`` of a forest's status words.  Synchronises the stream (reads them)."""
+    _dev(status, torch.int64, "status")
+    if status.dim() != 1 or status.shape[0] != 4:
+        raise ValueError("status must be the int64 [4] words of groups_init, got %s" % (tuple(status.shape),))
+    chains, edges, hooks, flags = (int(v) for v in status.cpu().tolist())
+    return {"chains": chains, "edges": edges, "hooks": hooks, "flags": flags}
+
+
 def range_select(scores, threshold, diag=None, capacity=None):
     """``(offsets int64 [m + 1], ids int64 [hits], scores fp32 [hits])``: the deterministic threshold compaction of an fp32 score
     matrix ``[m, n]`` (rows contiguous, any stride) into the CSR of include/mdx.h (``mdx_range_select``): hits ``s >= threshold``,

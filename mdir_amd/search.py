@@ -24,6 +24,11 @@ DBA and of the diffusion graph) as a :data:`KnnResult`.  With an int8 ``index`` 
 resolve (``include/mdx.h``, "exact kNN join"): a lower bound of every row's own k-th score from the int8 shard, the join kernel
 at that per-row threshold, the exact chain on the candidates.  With ``index=None`` it is the exact route, ``scores_rowmajor`` (or
 an fp32 index) + ``topk`` on chunks of rows.  Both routes return the same bits.
+
+``duplicate_groups(index, rows, threshold)`` is what a user of ``self_join`` usually wants: not the pairs but the groups they form,
+the connected components of the self-join's graph, at up to 8 thresholds from one pass of the join kernel, as a :data:`Groups`.
+The candidates of each chunk go straight into a lock-free union-find on the device (``include/mdx.h``, "near-duplicate groups") and
+are dropped again: N integers per threshold are kept, never a pair list.  Both routes return the same labels.
 """
 from collections import namedtuple
 
@@ -38,6 +43,13 @@ RangeResult.__doc__ = """CSR over the queries (the rows i of a self-join): offse
 KnnResult = namedtuple("KnnResult", ["ids", "scores", "pruned_rows"])
 KnnResult.__doc__ = """ids int64 [N, k], scores fp32 [N, k]: every row's exact top-k in rank order (its own match included);
 pruned_rows: the rows whose list came from the int8 route (0 on the exact route)."""
+
+Groups = namedtuple("Groups", ["labels", "offsets", "members", "stats"])
+Groups.__doc__ = """labels int64 [N] (one threshold) or [T, N] (a sequence): the smallest row id of every row's group, so ``labels[i] == i``
+exactly for the representatives.  offsets int64 [G + 1], members int64 [N]: the CSR of the groups in ascending label order, the
+members of each in ascending id, singletons included -- ``members[offsets[:-1]]`` are the representatives; for a sequence of
+thresholds, lists of T such tensors.  stats: ``{"chains", "edges", "hooks", "candidates"}``, the device counters of include/mdx.h
+and the candidates the join kernel reported (0 on the exact route)."""
 
 SearchResult = namedtuple("SearchResult", ["ids", "scores", "certified", "fallback"])
 SearchResult.__doc__ = """ids int64 [nq, k], scores fp32 [nq, k]; certified int32 [nq] (int8 index) or None (fp16);
@@ -332,3 +344,97 @@ def knn_join(index, rows, k, chunk=None, capacity=None):
         if exact is not None:
             exact.close()
     return KnnResult(ids, sims, pruned)
+
+
+# ------------------------------------------------------------------------------------------------------ near-duplicate groups
+
+def split_rows(lo, hi):
+    """The two halves ``((lo, mid), (mid, hi))`` of the row range ``[lo, hi)`` of a chunk whose candidates were too many, cut at a
+    multiple of ``JOIN_BLOCK`` rows from ``lo`` (itself one); None for a single block, which cannot be split."""
+    blocks = -(-(hi - lo) // ops.JOIN_BLOCK)
+    if blocks <= 1:
+        return None
+    mid = lo + blocks // 2 * ops.JOIN_BLOCK
+    return (lo, mid), (mid, hi)
+
+
+def _group_csr(labels):
+    """(offsets, members) of one level's labels: a stable sort keeps the members of a group in ascending id."""
+    vals, members = torch.sort(labels, stable=True)
+    _, counts = torch.unique_consecutive(vals, return_counts=True)
+    offsets = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=labels.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return offsets, members
+
+
+def duplicate_groups(index, rows, threshold, chunk=None, max_candidates=1 << 26):
+    """The groups of near-duplicates of ``rows`` (fp32 ``[N, D]`` on the device): the connected components of the graph whose edges
+    are the pairs :func:`self_join` reports at ``threshold``, as a :data:`Groups`.  ``threshold``: a number, or a sequence of at most
+    8 (any order, duplicates allowed) -- all of them from ONE pass of the join kernel, at the smallest.
+
+    ``index``: an int8 ``DescriptorIndex`` of ``rows``; per chunk (a multiple of 128 rows, default 32 768, as ``self_join``)
+    ``join_candidates`` -> ``groups_union_pairs``, and the candidates are dropped before the next chunk.  A chunk with more than
+    ``max_candidates`` candidates is split in halves and run again; a single 128-row block runs at its counted size.  Pairs whose
+    rows are already in one group are never scored, so a cluster of many identical rows costs little more than its candidates'
+    listing.  ``index=None``: the exact route, the fp32 score blocks of ``self_join``'s into ``groups_union_dense``.  The labels
+    depend on the rows and thresholds only."""
+    _check_rows(index, rows)
+    single = isinstance(threshold, (bool, int, float))
+    if not single and (not isinstance(threshold, (list, tuple)) or not 1 <= len(threshold) <= ops.GROUPS_MAX_T):
+        raise ValueError("threshold must be a number or a sequence of 1 to %d numbers, got %r" % (ops.GROUPS_MAX_T, threshold))
+    taus = [ops._tau(t) for t in ([threshold] if single else threshold)]
+    if chunk is not None:
+        _check_count(chunk, "chunk")
+    _check_count(max_candidates, "max_candidates")
+    n, d = rows.shape
+    if n > ops._MAX_ITEMS:
+        raise ValueError("duplicate_groups: %d rows, the forest holds at most 2^31 - 1" % n)
+    parent, status = ops.groups_init(len(taus), n, rows.device)
+    candidates = 0
+    if index is None:
+        if chunk is None:                                     # ~256 MB of fp32 scores per block
+            chunk = max(ops.JOIN_BLOCK, (1 << 28) // (4 * n) // ops.JOIN_BLOCK * ops.JOIN_BLOCK)
+        fp32 = None if d % 4 == 0 else ops.DescriptorIndex(rows, "ND")
+        try:
+            for lo in range(0, n, chunk):
+                hi = min(n, lo + chunk)
+                if fp32 is None:                              # the upper triangle only: columns lo .. n-1, read in place
+                    ops.groups_union_dense(ops.scores_rowmajor(rows[lo:], rows[lo:hi], "ND"), lo, lo, taus, parent, status)
+                else:
+                    ops.groups_union_dense(fp32.scores(rows[lo:hi], "ND"), lo, 0, taus, parent, status)
+        finally:
+            if fp32 is not None:
+                fp32.close()
+    else:
+        chunk = 1 << 15 if chunk is None else -(-chunk // ops.JOIN_BLOCK) * ops.JOIN_BLOCK
+        stats = _join_stats(index, rows)
+        tmin, capacity = min(taus), 1 << 20
+        for start in range(0, n, chunk):
+            work = [(start, min(n, start + chunk))]
+            while work:
+                lo, hi = work.pop()
+                pairs, count = ops.join_candidates(index, stats, index, stats, tmin, lo, hi, True, min(capacity, max_candidates))
+                halves = split_rows(lo, hi) if count > max_candidates else None
+                if halves is not None:
+                    del pairs
+                    work.extend(reversed(halves))
+                    continue
+                if count > pairs.numel():                     # the kernel counted on: run again at the exact size
+                    if count > ops._MAX_ITEMS:
+                        raise ValueError("%d candidates in one 128-row block, more than one call holds (2^31 - 1)" % count)
+                    del pairs
+                    pairs, count = ops.join_candidates(index, stats, index, stats, tmin, lo, hi, True, count)
+                capacity = max(capacity, pairs.numel())
+                candidates += count
+                if count:
+                    ops.groups_union_pairs(rows, pairs, taus, parent, status)
+                del pairs
+    labels = ops.groups_labels(parent)
+    st = ops.groups_status(status)
+    if st["flags"]:
+        raise ops._lib.MdxError("duplicate_groups: the union kernels set flags %#x (1: a loop gave up, 2: a pair out of range)" % st["flags"])
+    csr = [_group_csr(labels[t]) for t in range(len(taus))]
+    stats = {"chains": st["chains"], "edges": st["edges"], "hooks": st["hooks"], "candidates": candidates}
+    if single:
+        return Groups(labels[0], csr[0][0], csr[0][1], stats)
+    return Groups(labels, [c[0] for c in csr], [c[1] for c in csr], stats)
