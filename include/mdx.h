@@ -938,6 +938,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * exported, bound, and has cases in tests/test_gpu_groups_memcontract.py). */
 #include "mdx_groups.h"
 
+/* --------------------------------------------------------------- k-reciprocal re-ranking */
+
+/* k-reciprocal encoding (Zhong et al., CVPR 2017) beside alpha-QE, DBA and diffusion: the reciprocal sets of the database's kNN lists
+ * (R(i, k) and R(i, ceil(k / 2))), the sparse raw and locally expanded codes of every database row as CSRs, and per query the
+ * Jaccard min-sum of its code against the codes of its top-R first-stage rows, blended with the first-stage score by lam; rows
+ * outside the shortlist keep s - 3.  The whole contract -- sets, expansion, weights, summation orders, the static cap
+ * (MDX_KRECIP_MAX_K1 = 64, MDX_KRECIP_MAX_NNZ = 4096, MDX_KRECIP_MAX_R = 4096), the refusals -- is stated in mdx_krecip.h, beside this
+ * file, with the prototypes; their names are in _lib.KRECIP_EXPORTS, for the reason given above for mdx_knn_join.h, and their census
+ * is tests/test_krecip_host.py (every prototype is exported, bound, and -- unless it is a size function -- has cases in
+ * tests/test_gpu_krecip_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_krecip.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

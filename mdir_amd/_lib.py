@@ -36,7 +36,7 @@ ABI_VERSION = 3        # include/mdx.h MDX_ABI_VERSION this binding was written 
 def build(force=False):
     """Compile libmdx.so with hipcc --offload-arch=gfx950 (see csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h", "mdx_groups.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h", "mdx_groups.h", "mdx_krecip.h")]
     stale = not os.path.exists(LIB_PATH) or \
         any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -104,6 +104,13 @@ def _declare(lib):
         "mdx_groups_union_pairs": (i32, [p, i64, i64, p, i64, ctypes.POINTER(ctypes.c_float), i64, p, i64, p, p]),
         "mdx_groups_union_dense": (i32, [p, i64, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_float), i64, p, i64, p, p]),
         "mdx_groups_labels": (i32, [p, i64, i64, p, p]),
+        "mdx_krecip_sets": (i32, [p, i64, i64, p, p, p, p, p]),
+        "mdx_krecip_raw_offsets": (i32, [i64, i64, p, p, p, p, p, p]),
+        "mdx_krecip_raw_fill": (i32, [p, i64, i64, p, p, i64, i64, p, p, p, p, p, p, p, i64, p]),
+        "mdx_krecip_expand_offsets": (i32, [p, i64, i64, i64, p, p, i64, p, p]),
+        "mdx_krecip_expand_fill": (i32, [p, i64, i64, i64, p, p, p, i64, p, p, p, i64, p]),
+        "mdx_krecip_rerank_workspace": (i64, [i64, i64]),
+        "mdx_krecip_rerank": (i32, [p, p, p, i64, i64, i64, p, p, p, i64, p, p, p, i64, p, i64, p, i64, i64, f32, p, i64, p, i64, p]),
         "mdx_bn_act_f16": (i32, [p, p, i64, i64, i64, p, p, p, p, f32, i32, p]),
         "mdx_pool_l2n_f16": (i32, [p, i32, i32, i32, i32, i32, f32, f32, f32, p, p]),
         "mdx_pool_multi_f16": (i32, [pp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32, f32, f32, p, p]),
@@ -189,6 +196,11 @@ TRUNK_F16_EXPORTS = ("mdx_bn_act_f16", "mdx_pool_l2n_f16", "mdx_pool_multi_f16")
 # include/mdx_groups.h (included by mdx.h): the near-duplicate groups, apart from EXPORTS for the same reason; the census of these
 # is tests/test_groups_host.py (include/mdx.h, "near-duplicate groups")
 GROUPS_EXPORTS = ("mdx_groups_init", "mdx_groups_union_pairs", "mdx_groups_union_dense", "mdx_groups_labels")
+
+# include/mdx_krecip.h (included by mdx.h): k-reciprocal re-ranking, apart from EXPORTS for the same reason; the census of these is
+# tests/test_krecip_host.py (include/mdx.h, "k-reciprocal re-ranking")
+KRECIP_EXPORTS = ("mdx_krecip_sets", "mdx_krecip_raw_offsets", "mdx_krecip_raw_fill", "mdx_krecip_expand_offsets",
+                  "mdx_krecip_expand_fill", "mdx_krecip_rerank_workspace", "mdx_krecip_rerank")
 
 
 def lib():

@@ -1281,6 +1281,188 @@ def diffusion_truncated(graph, scores, top_ids, top_sims, kq, gamma, alpha, iter
     return (out, residual, steps) if return_residual else out
 
 
+# ------------------------------------------------------------------ k-reciprocal re-ranking
+
+KRECIP_MAX_K1 = 64                # include/mdx_krecip.h MDX_KRECIP_MAX_K1: one lane per list entry
+KRECIP_MAX_NNZ = 4096             # MDX_KRECIP_MAX_NNZ: k2 * k1 * (1 + ceil(k1 / 2)) at most; a code lives in LDS
+KRECIP_MAX_R = 4096               # MDX_KRECIP_MAX_R: the shortlist of one query
+
+
+def _krecip_lists(ids, who):
+    """(n, k) of the database lists ``ids`` int64 ``[N, k]``, ``k <= KRECIP_MAX_K1``."""
+    _dev(ids, torch.int64, "ids")
+    if ids.dim() != 2 or ids.shape[0] < 1 or not 1 <= ids.shape[1] <= KRECIP_MAX_K1:
+        raise ValueError("%s: ids must be [N, k] with N >= 1 and 1 <= k <= %d, got %s" % (who, KRECIP_MAX_K1, tuple(ids.shape)))
+    return ids.shape
+
+
+def _krecip_k2(k, k2, who):
+    if isinstance(k2, bool) or not isinstance(k2, int) or not 1 <= k2 <= k:
+        raise ValueError("%s: k2 must be an integer in [1, k] = [1, %d], got %r" % (who, k, k2))
+    if k2 * k * (1 + (k + 1) // 2) > KRECIP_MAX_NNZ:
+        raise ValueError("%s: k2 * k * (1 + ceil(k / 2)) = %d > KRECIP_MAX_NNZ = %d (k=%d k2=%d)"
+                         % (who, k2 * k * (1 + (k + 1) // 2), KRECIP_MAX_NNZ, k, k2))
+
+
+def _krecip_sets(sets, n, k, who):
+    rk, rk_counts, rh, rh_counts = sets
+    h = (k + 1) // 2
+    for t, name in ((rk, "rk"), (rk_counts, "rk_counts"), (rh, "rh"), (rh_counts, "rh_counts")):
+        _dev(t, torch.int32, name)
+    if tuple(rk.shape) != (n, k) or tuple(rh.shape) != (n, h) or tuple(rk_counts.shape) != (n,) or tuple(rh_counts.shape) != (n,):
+        raise ValueError("%s: sets of krecip_sets expected (rk [%d, %d], rk_counts [%d], rh [%d, %d], rh_counts [%d]), got %s, %s, %s, %s"
+                         % (who, n, k, n, n, h, n, tuple(rk.shape), tuple(rk_counts.shape), tuple(rh.shape), tuple(rh_counts.shape)))
+    return [_vp(t.data_ptr()) for t in sets]
+
+
+def _krecip_csr(csr, n, who, what, values=True):
+    """(offsets, cols, vals pointers, nnz) of a CSR ``(offsets int64 [n + 1], cols int32 [nnz], vals fp32 [nnz])``."""
+    offsets, cols, vals = csr
+    _dev(offsets, torch.int64, what + " offsets")
+    _dev(cols, torch.int32, what + " cols")
+    if values:
+        _dev(vals, torch.float32, what + " vals")
+    if tuple(offsets.shape) != (n + 1,) or cols.dim() != 1 or (values and tuple(vals.shape) != tuple(cols.shape)):
+        raise ValueError("%s: %s CSR expected (offsets [%d], cols [nnz], vals [nnz]), got %s, %s, %s"
+                         % (who, what, n + 1, tuple(offsets.shape), tuple(cols.shape), tuple(vals.shape) if values else None))
+    nnz = cols.shape[0]
+    return (_vp(offsets.data_ptr()), _vp(cols.data_ptr()) if nnz else None, _vp(vals.data_ptr()) if nnz and values else None, nnz)
+
+
+def krecip_sets(ids):
+    """The reciprocal sets of the database lists ``ids`` int64 ``[N, k]`` (``mdx_krecip_sets``; the definition is in
+    ``include/mdx_krecip.h``): ``(rk int32 [N, k], rk_counts int32 [N], rh int32 [N, ceil(k / 2)], rh_counts int32 [N])``, each
+    row's members first in list order, then -1."""
+    n, k = _krecip_lists(ids, "krecip_sets")
+    h = (k + 1) // 2
+    rk = torch.empty((n, k), dtype=torch.int32, device=ids.device)
+    rk_counts = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    rh = torch.empty((n, h), dtype=torch.int32, device=ids.device)
+    rh_counts = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_krecip_sets(_vp(ids.data_ptr()), n, k, _vp(rk.data_ptr()), _vp(rk_counts.data_ptr()),
+                                         _vp(rh.data_ptr()), _vp(rh_counts.data_ptr()), _stream()), "mdx_krecip_sets")
+    return rk, rk_counts, rh, rh_counts
+
+
+def krecip_raw_offsets(sets):
+    """``offsets`` int64 ``[N + 1]`` of the raw codes (``mdx_krecip_raw_offsets``: count pass and scan on the device) from the
+    ``sets`` of :func:`krecip_sets`.  ``offsets[N]`` is the nnz; nothing is read back here."""
+    rk = sets[0]
+    _dev(rk, torch.int32, "rk")
+    if rk.dim() != 2 or rk.shape[0] < 1 or not 1 <= rk.shape[1] <= KRECIP_MAX_K1:
+        raise ValueError("krecip_raw_offsets: rk must be [N, k] with N >= 1 and 1 <= k <= %d, got %s" % (KRECIP_MAX_K1, tuple(rk.shape)))
+    n, k = rk.shape
+    ptrs = _krecip_sets(sets, n, k, "krecip_raw_offsets")
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=rk.device)
+    with _on(rk):
+        check(_lib.lib().mdx_krecip_raw_offsets(n, k, *ptrs, _vp(offsets.data_ptr()), _stream()), "mdx_krecip_raw_offsets")
+    return offsets
+
+
+def krecip_raw_fill(rows, ids, sims, sets, offsets, nnz):
+    """``(cols int32 [nnz], vals fp32 [nnz])`` of the raw codes (``mdx_krecip_raw_fill``): ``rows`` fp32 ``[N, D]`` (contiguous
+    rows; a column slice is fine), the lists ``ids`` / ``sims`` ``[N, k]``, the ``sets`` of :func:`krecip_sets`, ``offsets`` of
+    :func:`krecip_raw_offsets` and ``nnz = offsets[N]``."""
+    n, k = _krecip_lists(ids, "krecip_raw_fill")
+    _dev(sims, torch.float32, "sims")
+    if tuple(sims.shape) != (n, k):
+        raise ValueError("krecip_raw_fill: sims must be [%d, %d] as ids, got %s" % (n, k, tuple(sims.shape)))
+    rp, ld = _rows(rows, "rows")
+    if rows.shape[0] != n:
+        raise ValueError("krecip_raw_fill: rows must be [%d, D], got %s" % (n, tuple(rows.shape)))
+    ptrs = _krecip_sets(sets, n, k, "krecip_raw_fill")
+    _dev(offsets, torch.int64, "offsets")
+    if tuple(offsets.shape) != (n + 1,) or isinstance(nnz, bool) or not isinstance(nnz, int) or nnz < 0:
+        raise ValueError("krecip_raw_fill: offsets int64 [%d] and an integer nnz >= 0 expected, got %s and %r"
+                         % (n + 1, tuple(offsets.shape), nnz))
+    cols = torch.empty((nnz,), dtype=torch.int32, device=ids.device)
+    vals = torch.empty((nnz,), dtype=torch.float32, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_krecip_raw_fill(rp, ld, rows.shape[1], _vp(ids.data_ptr()), _vp(sims.data_ptr()), n, k, *ptrs,
+                                             _vp(offsets.data_ptr()), _vp(cols.data_ptr()) if nnz else None,
+                                             _vp(vals.data_ptr()) if nnz else None, nnz, _stream()), "mdx_krecip_raw_fill")
+    return cols, vals
+
+
+def krecip_expand_offsets(ids, k2, raw):
+    """``offsets`` int64 ``[N + 1]`` of the expanded codes (``mdx_krecip_expand_offsets``) from the raw CSR ``raw = (offsets,
+    cols, vals)`` (``vals`` is not read and may be None)."""
+    n, k = _krecip_lists(ids, "krecip_expand_offsets")
+    _krecip_k2(k, k2, "krecip_expand_offsets")
+    ro, rc, _, rnnz = _krecip_csr(raw, n, "krecip_expand_offsets", "raw", values=False)
+    offsets = torch.empty((n + 1,), dtype=torch.int64, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_krecip_expand_offsets(_vp(ids.data_ptr()), n, k, k2, ro, rc, rnnz, _vp(offsets.data_ptr()), _stream()),
+              "mdx_krecip_expand_offsets")
+    return offsets
+
+
+def krecip_expand_fill(ids, k2, raw, offsets, nnz):
+    """``(cols int32 [nnz], vals fp32 [nnz])`` of the expanded codes (``mdx_krecip_expand_fill``), ``offsets`` of
+    :func:`krecip_expand_offsets` and ``nnz = offsets[N]``."""
+    n, k = _krecip_lists(ids, "krecip_expand_fill")
+    _krecip_k2(k, k2, "krecip_expand_fill")
+    ro, rc, rv, rnnz = _krecip_csr(raw, n, "krecip_expand_fill", "raw")
+    _dev(offsets, torch.int64, "offsets")
+    if tuple(offsets.shape) != (n + 1,) or isinstance(nnz, bool) or not isinstance(nnz, int) or nnz < 0:
+        raise ValueError("krecip_expand_fill: offsets int64 [%d] and an integer nnz >= 0 expected, got %s and %r"
+                         % (n + 1, tuple(offsets.shape), nnz))
+    cols = torch.empty((nnz,), dtype=torch.int32, device=ids.device)
+    vals = torch.empty((nnz,), dtype=torch.float32, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_krecip_expand_fill(_vp(ids.data_ptr()), n, k, k2, ro, rc, rv, rnnz, _vp(offsets.data_ptr()),
+                                                _vp(cols.data_ptr()) if nnz else None, _vp(vals.data_ptr()) if nnz else None, nnz,
+                                                _stream()), "mdx_krecip_expand_fill")
+    return cols, vals
+
+
+def krecip_rerank(half_sets, kth, k, k2, raw, expanded, scores, top_ids, lam, out=None):
+    """k-reciprocal scores ``[nq, N]`` (``mdx_krecip_rerank``; the definition is in ``include/mdx_krecip.h``): for the rows of
+    each query's shortlist ``top_ids`` int64 ``[nq, R]`` (:func:`topk` of ``scores``, ``R <= 4096``)
+    ``(1 - lam) * m / (2 - m) + lam * (1 + s) / 2``, ``m`` the min-sum of the query's code and the row's; elsewhere
+    ``scores - 3``.  ``half_sets = (rh, rh_counts)`` of :func:`krecip_sets`, ``kth`` fp32 ``[N]`` the k-th score of every
+    database list, ``raw`` / ``expanded`` the two CSRs.  ``out`` may be ``scores`` (in place).  Reads nothing back."""
+    rh, rh_counts = half_sets
+    _dev(rh, torch.int32, "rh")
+    _dev(rh_counts, torch.int32, "rh_counts")
+    _dev(kth, torch.float32, "kth")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KRECIP_MAX_K1:
+        raise ValueError("krecip_rerank: k must be an integer in [1, %d], got %r" % (KRECIP_MAX_K1, k))
+    _krecip_k2(k, k2, "krecip_rerank")
+    lam = _finite(lam, "lam", 0.0, None)
+    if lam > 1.0:
+        raise ValueError("lam must be in [0, 1], got %r" % (lam,))
+    n, h = kth.shape[0], (k + 1) // 2
+    if kth.dim() != 1 or n < 1 or tuple(rh.shape) != (n, h) or tuple(rh_counts.shape) != (n,):
+        raise ValueError("krecip_rerank: rh [N, %d], rh_counts [N] and kth [N] expected, got %s, %s, %s"
+                         % (h, tuple(rh.shape), tuple(rh_counts.shape), tuple(kth.shape)))
+    ro, rc, rv, rnnz = _krecip_csr(raw, n, "krecip_rerank", "raw")
+    eo, ec, ev, ennz = _krecip_csr(expanded, n, "krecip_rerank", "expanded")
+    sp, ld = _rows(scores, "scores")
+    nq = scores.shape[0]
+    if scores.shape[1] != n:
+        raise ValueError("scores must be [nq, %d], got %s" % (n, tuple(scores.shape)))
+    _dev(top_ids, torch.int64, "top_ids")
+    if top_ids.dim() != 2 or top_ids.shape[0] != nq:
+        raise ValueError("top_ids must be [%d, R], got %s" % (nq, tuple(top_ids.shape)))
+    r = top_ids.shape[1]
+    if not 1 <= r <= min(n, KRECIP_MAX_R):
+        raise ValueError("R = %d must be in [1, min(N, %d)]" % (r, KRECIP_MAX_R))
+    if out is None:
+        out = torch.empty((nq, n), dtype=torch.float32, device=scores.device)
+    elif tuple(out.shape) != (nq, n):
+        raise ValueError("out must be [%d,%d]" % (nq, n))
+    op, ld_out = _rows(out, "out")
+    h_ = _lib.lib()
+    ws = _workspace(h_.mdx_krecip_rerank_workspace(nq, r), scores.device)
+    with _on(scores):
+        check(h_.mdx_krecip_rerank(_vp(rh.data_ptr()), _vp(rh_counts.data_ptr()), _vp(kth.data_ptr()), n, k, k2, ro, rc, rv, rnnz,
+                                   eo, ec, ev, ennz, sp, ld, _vp(top_ids.data_ptr()), nq, r, lam, op, ld_out, _vp(ws.data_ptr()),
+                                   ws.numel(), _stream()), "mdx_krecip_rerank")
+    return out
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)

@@ -1,7 +1,8 @@
 """Re-ranking of the revisited Oxford/Paris protocol: alpha-weighted query expansion (alpha-QE) and database-side
 augmentation (DBA), as the GeM paper defines them (Radenovic, Tolias, Chum, "Fine-tuning CNN image retrieval with no human
 annotation", TPAMI 2018), and diffusion on a mutual kNN graph of the database (Iscen et al., "Efficient diffusion on region
-manifolds", CVPR 2017).  Not in the reference: the vendored cirtorch ships none of them.
+manifolds", CVPR 2017), and k-reciprocal encoding (Zhong et al., "Re-ranking person re-identification with k-reciprocal
+encoding", CVPR 2017) in its database-side form.  Not in the reference: the vendored cirtorch ships none of them.
 
 Both are built from the library's own pieces -- the exact similarity (``mdx_scores_rowmajor`` or an index), the top-k of
 ``mdx_topk`` (descending score, ascending id on ties) and the weighted gather-and-normalise ``mdx_knn_aggregate``, whose
@@ -199,3 +200,106 @@ def diffusion(qvecs, vecs, graph=None, kq=10, alpha=0.99, iters=20, tol=1e-6, in
     seed_ids, seed_sims = ops.topk(first, min(kq, n))
     return ops.diffusion(graph, first, seed_ids, seed_sims, graph.gamma, alpha, iters, tol, out=out,
                          return_residual=return_residual)
+
+
+# ---------------------------------------------------------------------------------------------------------- k-reciprocal
+
+K_RECIPROCAL_DEFAULTS = {"k1": 20, "k2": 6, "lam": 0.3, "truncate": 1000}
+
+
+def _check_krecip(k1, k2):
+    _check_int(k1, "k1")
+    _check_int(k2, "k2")
+    if k1 > ops.KRECIP_MAX_K1:
+        raise ValueError("k1 must be <= %d, got %r" % (ops.KRECIP_MAX_K1, k1))
+    if k2 > k1:
+        raise ValueError("k2 must be <= k1 = %d, got %r" % (k1, k2))
+    if k2 * k1 * (1 + (k1 + 1) // 2) > ops.KRECIP_MAX_NNZ:
+        raise ValueError("k2 * k1 * (1 + ceil(k1 / 2)) = %d exceeds %d (k1=%d, k2=%d): the codes are bounded statically"
+                         % (k2 * k1 * (1 + (k1 + 1) // 2), ops.KRECIP_MAX_NNZ, k1, k2))
+
+
+class ReciprocalEncoding:
+    """The k-reciprocal codes of the database ``vecs`` ``[N, D]`` that :func:`k_reciprocal` compares the queries with
+    (definition in ``include/mdx_krecip.h``).  Built once per database, like :class:`DiffusionGraph`: the neighbour lists of
+    :func:`search.knn_join` (``k = min(k1, N)``; the exact route ``chunk`` rows at a time, or pruned on ``index``, an int8
+    ``DescriptorIndex`` of ``vecs``), the reciprocal sets, the raw codes and their local expansion over the first ``min(k2, k)``
+    list entries.  The lists, and so every bit here, depend on neither the chunk nor the index.  Each CSR reads its nnz back once
+    (synchronises).
+
+    Attributes: ``rk`` / ``rh`` int32 ``[N, k]`` / ``[N, ceil(k / 2)]`` with ``rk_counts`` / ``rh_counts`` int32 ``[N]`` (the two
+    ELLs); ``raw`` and ``expanded``, each ``(offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz])``; ``kth`` fp32 ``[N]`` (the
+    k-th score of every list); ``n``, ``k`` (``min(k1, N)``), ``k1``, ``k2``.  ``layout="DN"`` accepts the reference's ``[D, N]``
+    matrix through one transpose copy."""
+
+    def __init__(self, vecs, k1=20, k2=6, chunk=None, layout="ND", index=None):
+        _check_krecip(k1, k2)
+        if chunk is not None:
+            _check_int(chunk, "chunk")
+        if layout in ("DN", "dim_major", _lib.MDX_DIM_MAJOR):
+            vecs = vecs.t().contiguous()
+        elif layout not in ("ND", "row_major", _lib.MDX_ROW_MAJOR):
+            raise ValueError("unknown layout %r" % (layout,))
+        if vecs.dim() != 2:
+            raise ValueError("vecs must be 2-d, got %s" % (tuple(vecs.shape),))
+        n = vecs.shape[0]
+        k = min(k1, n)
+        ids, sims = _neighbours(vecs, k, chunk, index)
+        sets = ops.krecip_sets(ids)
+        self.rk, self.rk_counts, self.rh, self.rh_counts = sets
+        offsets = ops.krecip_raw_offsets(sets)
+        nnz = int(offsets[n].item())
+        self.raw = (offsets,) + ops.krecip_raw_fill(vecs, ids, sims, sets, offsets, nnz)
+        kk = min(k2, k)
+        offsets = ops.krecip_expand_offsets(ids, kk, self.raw)
+        nnz = int(offsets[n].item())
+        self.expanded = (offsets,) + ops.krecip_expand_fill(ids, kk, self.raw, offsets, nnz)
+        self.kth = sims[:, k - 1].contiguous()
+        self.n, self.k, self.k1, self.k2 = n, k, k1, k2
+
+    def nnz(self):
+        """``(raw, expanded)`` stored entries."""
+        return self.raw[1].shape[0], self.expanded[1].shape[0]
+
+    def close(self):
+        self.rk = self.rk_counts = self.rh = self.rh_counts = self.raw = self.expanded = self.kth = None
+
+
+def k_reciprocal(qvecs, vecs, encoding=None, lam=0.3, truncate=1000, index=None, compute="chain", scores=None):
+    """k-reciprocal scores ``[Q, N]`` of the queries ``qvecs`` ``[Q, D]`` on the database ``vecs`` ``[N, D]``
+    (``mdx_krecip_rerank``; definition in ``include/mdx_krecip.h``): each query is encoded against the database's lists, and the
+    ``R = min(truncate, N)`` best first-stage rows get ``(1 - lam) * (1 - d_Jaccard) + lam * (1 + s) / 2``; every other row
+    keeps its first-stage score minus 3, so that rows outside the shortlist rank last, in first-stage order.
+
+    ``encoding`` is a :class:`ReciprocalEncoding` of ``vecs``; pass one to reuse it across batches.  When None, one is built here
+    with its defaults on the exact route (``index`` is the index of the first-stage similarity, as in :func:`diffusion`, and is not
+    handed to the neighbour join) and closed again before the call returns.  The first-stage scores come from ``scores`` when given (never written), else from the similarity of
+    ``vecs`` or ``index`` in mode ``compute`` (as :func:`query_expansion`) and are then solved in place.  A query that is a
+    database row finds its own row among the ``k2 - 1`` rows of its local expansion and counts it once more, as alpha-QE does.
+    ``truncate`` is an integer in ``[1, 4096]``, ``lam`` a number in ``[0, 1]``."""
+    _check_int(truncate, "truncate")
+    if truncate > ops.KRECIP_MAX_R:
+        raise ValueError("truncate must be in [1, %d], got %r" % (ops.KRECIP_MAX_R, truncate))
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam) or not 0 <= lam <= 1:
+        raise ValueError("lam must be a finite number in [0, 1], got %r" % (lam,))
+    if vecs.dim() != 2 or qvecs.dim() != 2 or qvecs.shape[1] != vecs.shape[1]:
+        raise ValueError("qvecs [Q, D] and vecs [N, D] expected, got %s and %s" % (tuple(qvecs.shape), tuple(vecs.shape)))
+    n = vecs.shape[0]
+    own = encoding is None
+    if own:
+        encoding = ReciprocalEncoding(vecs)
+    if encoding.n != n:
+        raise ValueError("encoding has %d rows, the database %d" % (encoding.n, n))
+    if scores is None:
+        first = _similarity(vecs, qvecs, index, compute)
+        out = first                                        # ours: solved in place
+    else:
+        if tuple(scores.shape) != (qvecs.shape[0], n):
+            raise ValueError("scores must be [%d, %d], got %s" % (qvecs.shape[0], n, tuple(scores.shape)))
+        first, out = scores, None
+    top_ids, _ = ops.topk(first, min(truncate, n))
+    res = ops.krecip_rerank((encoding.rh, encoding.rh_counts), encoding.kth, encoding.k, min(encoding.k2, encoding.k),
+                            encoding.raw, encoding.expanded, first, top_ids, float(lam), out=out)
+    if own:
+        encoding.close()                                   # the launches hold the stream's order; torch frees behind them
+    return res

@@ -29,9 +29,13 @@ sub-key ``truncate: R`` (``kq <= R <= 4096``; no default) solves each query on t
 single-process; not with the re-ranking keys) rescores each query's top-K rows of the compressed scores exactly
 (``ops.rescore``, the fp32 chain) and ranks by the composite: the rescored top-K, then every other row in the compressed
 order.  For int8 it prints the certified depth (``ops.rescore_certify``) per query: min / median / max.
-``neighbours: exact | i8`` (criterion key, default ``exact``; only with ``database_augmentation`` or ``diffusion``) chooses how
+``neighbours: exact | i8`` (criterion key, default ``exact``; only with ``database_augmentation``, ``diffusion`` or ``k_reciprocal``) chooses how
 their neighbour lists are built: ``i8`` prunes the all-pairs top-k on a temporary int8 index of the rows (``search.knn_join``);
 the lists, and so the results, are the same bits.
+``k_reciprocal: {k1, k2, lam, truncate}`` (criterion key, every sub-key optional, defaults 20, 6, 0.3, 1000) re-ranks each query's
+``truncate`` best rows by the Jaccard overlap of k-reciprocal codes (``rerank.k_reciprocal``), after DBA when both are set;
+with ``query_expansion`` the expanded queries' scores are its first stage; not together with ``diffusion`` or ``rescore``;
+single-process only; it honours ``neighbours: i8``.
 """
 import contextlib
 import gzip
@@ -120,13 +124,17 @@ class CirDatasetAp:
         self.diffusion = _diffusion_params(params.pop("diffusion", None))
         if self.diffusion and self.query_expansion:
             raise ValueError("diffusion together with query_expansion is not supported: choose one")
-        # how DBA and the diffusion graph get their neighbour lists: "exact" (fp32 scores of every pair) or "i8" (the same lists,
+        # k-reciprocal re-ranking (not in the reference): {k1, k2, lam, truncate}; None = off
+        self.k_reciprocal = _k_reciprocal_params(params.pop("k_reciprocal", None))
+        if self.k_reciprocal and self.diffusion:
+            raise ValueError("k_reciprocal together with diffusion is not supported: choose one")
+        # how DBA, the diffusion graph and the k-reciprocal encoding get their neighbour lists: "exact" (fp32 scores of every pair) or "i8" (the same lists,
         # pruned on a temporary int8 index of the rows: search.knn_join)
         self.neighbours = params.pop("neighbours", "exact")
         if self.neighbours not in ("exact", "i8"):
             raise ValueError("neighbours: 'exact' or 'i8', got %r" % (self.neighbours,))
-        if self.neighbours != "exact" and not (self.database_augmentation or self.diffusion):
-            raise ValueError("neighbours: %s builds the neighbour lists of database_augmentation / diffusion; neither is on"
+        if self.neighbours != "exact" and not (self.database_augmentation or self.diffusion or self.k_reciprocal):
+            raise ValueError("neighbours: %s builds the neighbour lists of database_augmentation / diffusion / k_reciprocal; neither is on"
                              % self.neighbours)
         for key in ("database_augmentation", "diffusion"):
             if self.neighbours == "i8" and getattr(self, key) and getattr(self, key)["k"] > ops.KNN_JOIN_MAX_K:
@@ -138,7 +146,7 @@ class CirDatasetAp:
             if self.storage not in {"i8", "f16"}:
                 raise ValueError("rescore: rescores the shortlist of an int8 or fp16 shard (storage: i8 / f16); storage is %s, "
                                  "whose scores are already exact" % self.storage)
-            others = [k for k in ("query_expansion", "database_augmentation", "diffusion") if getattr(self, k)]
+            others = [k for k in ("query_expansion", "database_augmentation", "diffusion", "k_reciprocal") if getattr(self, k)]
             if others:
                 raise ValueError("rescore together with %s is not supported" % " / ".join(others))
         if isinstance(self.dataset, dict):
@@ -168,6 +176,9 @@ class CirDatasetAp:
                              "%d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1 and self.diffusion:
             raise ValueError("%s: diffusion re-ranks in a single process (the graph spans the whole database); this run has "
+                             "%d ranks" % (self.dataset, _world_size()))
+        if _world_size() > 1 and self.k_reciprocal:
+            raise ValueError("%s: k_reciprocal re-ranks in a single process (the codes span the whole database); this run has "
                              "%d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1 and self.rescore:
             raise ValueError("%s: rescore runs in a single process for now; this run has %d ranks" % (self.dataset, _world_size()))
@@ -222,6 +233,13 @@ class CirDatasetAp:
                     scores = rerank.diffusion(qvecs, vecs, graph, kq=p["kq"], alpha=p["alpha"], iters=p["iters"],
                                               tol=p["tol"], scores=scores, truncate=truncate)
                     graph.close()
+            if self.k_reciprocal:
+                p = self.k_reciprocal
+                with range_("k_reciprocal"):
+                    with _neighbour_index(vecs, self.neighbours) as nix:
+                        encoding = rerank.ReciprocalEncoding(vecs, k1=p["k1"], k2=p["k2"], index=nix)
+                    scores = rerank.k_reciprocal(qvecs, vecs, encoding, lam=p["lam"], truncate=p["truncate"], scores=scores)
+                    encoding.close()
             if self.rescore:
                 averages, scores_per_query = self._rescored_map(vecs, qvecs, scores, index)
             elif self.ranking == "full":
@@ -322,6 +340,34 @@ def _diffusion_params(value):
         if isinstance(x, bool) or not isinstance(x, int) or not out["kq"] <= x <= ops.DIFFUSION_MAX_R:
             raise ValueError("diffusion: truncate must be an integer in [kq, %d] = [%d, %d], got %r"
                              % (ops.DIFFUSION_MAX_R, out["kq"], ops.DIFFUSION_MAX_R, x))
+    return out
+
+
+def _k_reciprocal_params(value):
+    """``{k1, k2, lam, truncate}`` of the ``k_reciprocal`` criterion key, each optional (the defaults of
+    ``rerank.K_RECIPROCAL_DEFAULTS``), validated (None: the key is absent)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict):
+        raise ValueError("k_reciprocal: a mapping with the optional keys k1, k2, lam, truncate, got %r" % (value,))
+    unknown = set(value) - set(rerank.K_RECIPROCAL_DEFAULTS)
+    if unknown:
+        raise ValueError("k_reciprocal: unknown keys %s (allowed: k1, k2, lam, truncate)" % sorted(unknown))
+    out = dict(rerank.K_RECIPROCAL_DEFAULTS, **value)
+    for key in ("k1", "k2", "truncate"):
+        x = out[key]
+        if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+            raise ValueError("k_reciprocal: %s must be an integer >= 1, got %r" % (key, x))
+    k1, k2 = out["k1"], out["k2"]
+    if k1 > ops.KRECIP_MAX_K1 or k2 > k1 or k2 * k1 * (1 + (k1 + 1) // 2) > ops.KRECIP_MAX_NNZ:
+        raise ValueError("k_reciprocal: k1 <= %d, k2 <= k1 and k2 * k1 * (1 + ceil(k1 / 2)) <= %d are required, got k1=%r k2=%r"
+                         % (ops.KRECIP_MAX_K1, ops.KRECIP_MAX_NNZ, k1, k2))
+    if out["truncate"] > ops.KRECIP_MAX_R:
+        raise ValueError("k_reciprocal: truncate must be an integer in [1, %d], got %r" % (ops.KRECIP_MAX_R, out["truncate"]))
+    x = out["lam"]
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or not 0 <= x <= 1:
+        raise ValueError("k_reciprocal: lam must be a finite number in [0, 1], got %r" % (x,))
+    out["lam"] = float(x)
     return out
 
 
