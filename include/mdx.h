@@ -950,6 +950,17 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * tests/test_gpu_krecip_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_krecip.h"
 
+/* --------------------------------------------------------------- photometric normalisation */
+
+/* The reference's other two photometric normalisations of the Lab lightness beside CLAHE, each fused with the input conversion like
+ * mdx_clahe_u8_to_chw: histogram matching (`match_histogram:eq` or a target CDF) and gamma equalisation (`gamma_equalize:<target>`).
+ * The whole contract -- the numpy / scipy arithmetic restated, the bin edges and centres, the secant iteration and its fallback, the
+ * workspace layout, the launches, the refusals -- is stated in mdx_photometric.h, beside this file, with the prototypes; their names
+ * are in _lib.PHOTOMETRIC_EXPORTS, for the reason given above for mdx_knn_join.h, and their census is
+ * tests/test_photometric_host.py (every prototype is exported and bound; the two conversions have cases in
+ * tests/test_gpu_photometric_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_photometric.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

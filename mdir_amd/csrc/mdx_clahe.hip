@@ -20,29 +20,14 @@
 //   apply   L8 + (a, b) + LUTs -> normalised fp32 CHW   (bilinear LUT blend, Lab -> RGB, (x - mean) / std)
 // The tile kernel must finish before any pixel can be finished (a pixel blends the LUTs of four tiles): the launch boundary is
 // the grid-wide dependency, not an accident.
-#include "mdx_common.h"
+#include "mdx_lab.h"
 
-// Every product and sum below is rounded on its own, as in OpenCV's scalar code (and in the numpy restatement): hipcc's
-// default contraction would fuse a*b + c*d into an fma and move the interpolation's exact .5 ties (HIP's __fmul_rn /
-// __fadd_rn are plain operators inlined from a header compiled WITH contraction, so they do not stop it: the helpers below do).
+// mdx_lab.h (the RGB <-> Lab code, shared with mdx_photometric.hip) defines its helpers -- mul_ / add_ / sub_ / div_ among them --
+// without contraction; the same holds for everything below: every product and sum is rounded on its own, as in OpenCV's scalar
+// code (and in the numpy restatement), so that the interpolation's exact .5 ties stay where they are.
 #pragma clang fp contract(off)
 
 namespace mdx {
-
-// defined HERE, under the pragma (the HIP header versions are inlined with the contraction flags of their own scope)
-__device__ __forceinline__ float mul_(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_(float a, float b) { return a + b; }
-__device__ __forceinline__ float sub_(float a, float b) { return a - b; }
-__device__ __forceinline__ float div_(float a, float b) { return a / b; }
-
-struct Lab { float L, a, b; };
-
-__device__ __forceinline__ float srgb_to_linear(float c)
-{
-    return c <= 0.04045f ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f);
-}
-
-__device__ __forceinline__ float lab_f(float t) { return t > 0.008856f ? cbrtf(t) : 7.787f * t + (float)(16.0 / 116.0); }
 
 // the uint8 lightness CLAHE sees: ((L + 0) / 100 * 255).astype(uint8) -- truncation (functional.py:117)
 __device__ __forceinline__ uint8_t lab_l8(float L) { return (uint8_t)(int)mul_(div_(L, 100.0f), 255.0f); }
@@ -53,24 +38,6 @@ __device__ __forceinline__ int reflect101(int i, int n)
     const int period = 2 * (n - 1);
     i = (i < 0 ? -i : i) % period;
     return i >= n ? period - i : i;
-}
-
-// RGB2Lab_f with the sRGB -> linear step looked up (lin[v] = srgb_to_linear(v / 255), the same call on the same 256 inputs)
-__device__ __forceinline__ Lab rgb8_to_lab_lut(const float *lin, uint8_t r8, uint8_t g8, uint8_t b8)
-{
-    const float r = lin[r8], g = lin[g8], b = lin[b8];
-    constexpr float m00 = (float)(0.412453 / 0.950456), m01 = (float)(0.357580 / 0.950456), m02 = (float)(0.180423 / 0.950456);
-    constexpr float m10 = 0.212671f, m11 = 0.715160f, m12 = 0.072169f;
-    constexpr float m20 = (float)(0.019334 / 1.088754), m21 = (float)(0.119193 / 1.088754), m22 = (float)(0.950227 / 1.088754);
-    const float x = add_(add_(mul_(r, m00), mul_(g, m01)), mul_(b, m02));
-    const float y = add_(add_(mul_(r, m10), mul_(g, m11)), mul_(b, m12));
-    const float z = add_(add_(mul_(r, m20), mul_(g, m21)), mul_(b, m22));
-    const float fx = lab_f(x), fy = lab_f(y), fz = lab_f(z);
-    Lab o;
-    o.L = y > 0.008856f ? sub_(mul_(116.0f, fy), 16.0f) : mul_(903.3f, y);
-    o.a = mul_(500.0f, sub_(fx, fy));
-    o.b = mul_(200.0f, sub_(fy, fz));
-    return o;
 }
 
 constexpr int CLAHE_TILE_THREADS = 512;
@@ -144,19 +111,9 @@ __global__ __launch_bounds__(CLAHE_TILE_THREADS) void clahe_tile_kernel(const ui
     luts[(int64_t)blockIdx.x * 256 + tid] = (uint8_t)fminf(fmaxf(r, 0.0f), 255.0f);
 }
 
-struct ClaheNorm { float mean[3], std[3]; };
-
-// linear -> sRGB on the OUTPUT side: c^(1/2.4) through the hardware's exp2 / log2 (a few ulp; nothing is truncated after it --
-// the value goes straight into (x - mean) / std -- and OpenCV itself interpolates a spline table here).  The INPUT side keeps
-// powf: its result is truncated to the uint8 lightness CLAHE sees, and it is evaluated 256 times per workgroup, not per pixel.
-__device__ __forceinline__ float linear_to_srgb_fast(float c)
-{
-    return c <= 0.0031308f ? c * 12.92f : 1.055f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (float)(1.0 / 2.4)) - 0.055f;
-}
-
 // one pixel: CLAHE_Interpolation_Body on its lightness, then Lab -> RGB -> (x - mean) / std
 __device__ __forceinline__ void clahe_finish_pixel(int x, int y, int v, float2 chroma, const uint8_t *__restrict__ luts_img, int tiles_x, int tiles_y,
-                                                   int tile_w, int tile_h, const ClaheNorm &nrm, uint8_t &l_eq, float (&o)[3])
+                                                   int tile_w, int tile_h, const LabNorm &nrm, uint8_t &l_eq, float (&o)[3])
 {
     // inv_tw = 1.0f / tileSize.width as an IEEE division (a plain `/` may become v_rcp_f32: one ulp off flips exact .5 ties below)
     const float txf = sub_(mul_((float)x, div_(1.0f, (float)tile_w)), 0.5f);
@@ -176,36 +133,8 @@ __device__ __forceinline__ void clahe_finish_pixel(int x, int y, int v, float2 c
     const float res = add_(mul_(top, ya1), mul_(bot, ya));
     const float l_new8 = fminf(fmaxf(rintf(res), 0.0f), 255.0f);
     l_eq = (uint8_t)l_new8;                         // the equalised lightness, kept for the caller (1 byte per pixel)
-    // back through the reference's normalised space: spc = (lab + [0,128,128]) / [100,255,255]; spc[0] = clahe / 255;
-    // lab' = spc * [100,255,255] - [0,128,128]   (float32 steps as written there)
-    const float L = mul_(div_(l_new8, 255.0f), 100.0f);
-    const float a = sub_(mul_(div_(add_(chroma.x, 128.0f), 255.0f), 255.0f), 128.0f);
-    const float b = sub_(mul_(div_(add_(chroma.y, 128.0f), 255.0f), 255.0f), 128.0f);
-    // Lab2RGB_f
-    constexpr float lthresh = (float)(0.008856 * 903.3), fthresh = (float)(7.787 * 0.008856 + 16.0 / 116.0);
-    float fy, yy;
-    if (L <= lthresh) {
-        yy = div_(L, 903.3f);
-        fy = add_(mul_(7.787f, yy), (float)(16.0 / 116.0));
-    } else {
-        fy = div_(add_(L, 16.0f), 116.0f);
-        yy = mul_(mul_(fy, fy), fy);
-    }
-    const float fx = add_(div_(a, 500.0f), fy), fz = sub_(fy, div_(b, 200.0f));
-    const float xx = fx <= fthresh ? div_(sub_(fx, (float)(16.0 / 116.0)), 7.787f) : mul_(mul_(fx, fx), fx);
-    const float zz = fz <= fthresh ? div_(sub_(fz, (float)(16.0 / 116.0)), 7.787f) : mul_(mul_(fz, fz), fz);
-    constexpr float k00 = (float)(3.240479 * 0.950456), k01 = -1.53715f, k02 = (float)(-0.498535 * 1.088754);
-    constexpr float k10 = (float)(-0.969256 * 0.950456), k11 = 1.875991f, k12 = (float)(0.041556 * 1.088754);
-    constexpr float k20 = (float)(0.055648 * 0.950456), k21 = -0.204043f, k22 = (float)(1.057311 * 1.088754);
-    float c[3];
-    c[0] = add_(add_(mul_(xx, k00), mul_(yy, k01)), mul_(zz, k02));
-    c[1] = add_(add_(mul_(xx, k10), mul_(yy, k11)), mul_(zz, k12));
-    c[2] = add_(add_(mul_(xx, k20), mul_(yy, k21)), mul_(zz, k22));
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float s = linear_to_srgb_fast(fminf(fmaxf(c[ch], 0.0f), 1.0f));
-        o[ch] = div_(sub_(s, nrm.mean[ch]), nrm.std[ch]);         // totensor (no scaling of a float image) | normalize
-    }
+    // spc[0] = clahe / 255, back on the 0..100 scale; the chroma's round trip and Lab -> RGB -> normalise are mdx_lab.h's
+    lab_finish_pixel(mul_(div_(l_new8, 255.0f), 100.0f), chroma, nrm, o);
 }
 
 // VEC = 4: a thread finishes four consecutive pixels of a row (W % 4 == 0): one 4-byte lightness load, two 16-byte chroma
@@ -213,7 +142,7 @@ __device__ __forceinline__ void clahe_finish_pixel(int x, int y, int v, float2 c
 template <int VEC>
 __global__ __launch_bounds__(256) void clahe_apply_kernel(const float2 *__restrict__ ab, const uint8_t *__restrict__ l8,
                                                           const uint8_t *__restrict__ luts, int H, int W, int tiles_x, int tiles_y,
-                                                          int tile_w, int tile_h, ClaheNorm nrm, uint8_t *__restrict__ l8_out,
+                                                          int tile_w, int tile_h, LabNorm nrm, uint8_t *__restrict__ l8_out,
                                                           float *__restrict__ out)
 {
     const int64_t hw = (int64_t)H * W;
@@ -298,7 +227,7 @@ int mdx_clahe_u8_to_chw(const uint8_t *rgb, int64_t B, int64_t H, int64_t W, int
     }
     hipLaunchKernelGGL(clahe_tile_kernel, dim3((unsigned)(B * tiles_x * tiles_y)), dim3(CLAHE_TILE_THREADS), 0, s, rgb, (int)H, (int)W, tiles_x,
                        tiles_y, tw, th, clip, l8, ab, luts);
-    ClaheNorm nrm;
+    LabNorm nrm;
     for (int c = 0; c < 3; ++c) {
         nrm.mean[c] = mean[c];
         nrm.std[c] = std[c];

@@ -5,8 +5,9 @@ CPU-side loader of the hot path; mirrors
 ``datahelpers.py:24-50`` (pil_loader, imresize), ``testdataset.py:4-38``
 (configdataset), ``utils/general.py:4-11`` (get_data_root) and mdir's transform DSL
 (``mdir/components/data/transform/__init__.py:35-44``, ``core_transforms.py:33-63``).
-Only the transforms eval.py uses are provided; CLAHE & co. are CPU/OpenCV
-preprocessing upstream of the tensor this path consumes.
+Only the transforms eval.py uses are provided, and the three photometric normalisations of the lightness (``apply_clahe``,
+``match_histogram``, ``gamma_equalize``: device work, see ``Compose.device_tail``); the other image transforms of the reference
+are CPU/OpenCV preprocessing upstream of the tensor this path consumes.
 """
 import os
 import pickle
@@ -280,6 +281,86 @@ class ApplyClahe:
                            "MDIR_AMD_GPU_PREPROCESS on): there is no CPU fallback")
 
 
+# name -> np.cumsum of a registered 256-bin lightness histogram, float64 and unnormalised as the reference keeps its own
+# (functional.HISTOGRAM_CDF); the reference's "f3d_lab" table is part of its program text and is not shipped here
+HISTOGRAM_CDF = {}
+
+
+def _histogram_cdf(histogram, what):
+    h = np.asarray(histogram, dtype=np.float64).reshape(-1)
+    if h.size != 256 or not np.isfinite(h).all() or (h < 0).any():
+        raise ValueError("%s: a histogram is 256 non-negative finite values, got %d%s"
+                         % (what, h.size, "" if h.size != 256 else " with negative or non-finite ones"))
+    return np.cumsum(h)
+
+
+def register_histogram(name, histogram):
+    """Makes ``match_histogram:<name>`` available: ``histogram`` is the target's 256 bin values over the lightness bins of
+    ``functional.HISTOGRAM_BINS`` (centres ``k / 255``), non-negative and finite; its ``np.cumsum`` is kept in float64."""
+    name = str(name)
+    if name == "eq" or not name:
+        raise ValueError("register_histogram: %r is not a name a histogram can take ('eq' is the equalisation)" % name)
+    HISTOGRAM_CDF[name] = _histogram_cdf(histogram, "register_histogram(%r)" % name)
+
+
+def _lookup_histogram_cdf(name):
+    """The CDF registered under ``name``, else of ``<name>.npy`` (the 256 bin values) in the directories model files are
+    looked up in (``scenario.resource_dirs()``: ``$MDIR_AMD_MODELS``, then ``<data root>/networks``); KeyError for neither."""
+    if name in HISTOGRAM_CDF:
+        return HISTOGRAM_CDF[name]
+    from .scenario import resource_dirs
+    for d in resource_dirs():
+        path = os.path.join(d, name + ".npy")
+        if os.path.isfile(path):
+            return _histogram_cdf(np.load(path, allow_pickle=False), path)
+    raise KeyError("match_histogram: no histogram %r: register it (datasets.register_histogram) or put %s.npy into one of %s"
+                   % (name, name, resource_dirs()))
+
+
+class MatchHistogram:
+    """``match_histogram:<histogram>[:colorspace]`` of the scenario DSL (``photometric_transforms.MatchHistogram``,
+    photometric_transforms.py:50-58): the lightness histogram of the image equalised (``eq``) or matched to a named target
+    (:func:`register_histogram`, or ``<name>.npy`` among the model files).  Device work like :class:`ApplyClahe`
+    (``mdx_histmatch_u8_to_chw``): this object carries the parameters, and calling it on the host raises."""
+
+    def __init__(self, histogram, colorspace="lab"):
+        self.histogram = str(histogram)
+        self.colorspace = str(colorspace).lower()
+        if self.colorspace != "lab":
+            raise NotImplementedError("match_histogram: colorspace %r (only 'lab')" % colorspace)
+        self.cdf = None if self.histogram == "eq" else _lookup_histogram_cdf(self.histogram)
+        self._on_device = {}
+
+    def device_cdf(self, device):
+        """The target CDF as a float64 tensor on ``device``: uploaded at the first call for that device, then kept."""
+        key = str(device)
+        if key not in self._on_device:
+            self._on_device[key] = torch.from_numpy(np.ascontiguousarray(self.cdf)).to(device)
+        return self._on_device[key]
+
+    def __call__(self, *pics):
+        raise RuntimeError("match_histogram runs on the MI355X only (chain `pil2np | match_histogram:<name> | totensor | "
+                           "normalize` with MDIR_AMD_GPU_PREPROCESS on): there is no CPU fallback")
+
+
+class GammaEqualize:
+    """``gamma_equalize:<target>[:colorspace]`` of the scenario DSL (``photometric_transforms.GammaEqualize``,
+    photometric_transforms.py:87-97): a gamma on the lightness that moves its mean to ``target``, 0 < target < 1.  Device
+    work like :class:`ApplyClahe` (``mdx_gamma_u8_to_chw``): this object carries the parameters, and calling it on the host raises."""
+
+    def __init__(self, target, colorspace="lab"):
+        self.target = float(target)
+        if not 0.0 < self.target < 1.0:
+            raise ValueError("gamma_equalize: target %r must lie in (0, 1)" % (target,))
+        self.colorspace = str(colorspace).lower()
+        if self.colorspace != "lab":
+            raise NotImplementedError("gamma_equalize: colorspace %r (only 'lab')" % colorspace)
+
+    def __call__(self, *pics):
+        raise RuntimeError("gamma_equalize runs on the MI355X only (chain `pil2np | gamma_equalize:<target> | totensor | "
+                           "normalize` with MDIR_AMD_GPU_PREPROCESS on): there is no CPU fallback")
+
+
 class Compose:
     def __init__(self, transforms):
         self.transforms = transforms
@@ -293,17 +374,25 @@ class Compose:
         """``(mean, std)`` when the whole chain is the PIL -> normalised CHW tensor conversion
         (``pil2np | totensor | normalize`` of the scenarios, or cirtorch's ``ToTensor, Normalize``):
         extraction then ships uint8 pixels and does this arithmetic on the GPU (``mdx_u8_to_chw``,
-        same fp32 operation order).  ``None`` for any other chain."""
+        same fp32 operation order).  ``(mean, std, parameters)`` when a photometric normalisation of the lightness stands
+        between ``pil2np`` and ``totensor``: ``apply_clahe`` (``{"clip_limit", "grid"}``), ``match_histogram`` or
+        ``gamma_equalize`` (a dict with an ``"op"`` key, see :func:`device_convert`).  ``None`` for any other chain."""
         t = list(self.transforms)
-        clahe = None
+        photometric = None
         if len(t) == 4 and isinstance(t[0], Pil2Numpy) and isinstance(t[1], ApplyClahe):
             # the CLAHE networks' chain: a third element carries the CLAHE parameters (mdx_clahe_u8_to_chw does all of it)
-            clahe, t = {"clip_limit": t[1].clip_limit, "grid": t[1].grid_size}, t[2:]
+            photometric, t = {"clip_limit": t[1].clip_limit, "grid": t[1].grid_size}, t[2:]
+        elif len(t) == 4 and isinstance(t[0], Pil2Numpy) and isinstance(t[1], MatchHistogram):
+            # "cdf": None for `eq`, otherwise device -> the 256 cumulative values there (uploaded once per device)
+            photometric, t = {"op": "match_histogram", "histogram": t[1].histogram,
+                              "cdf": t[1].device_cdf if t[1].cdf is not None else None}, t[2:]
+        elif len(t) == 4 and isinstance(t[0], Pil2Numpy) and isinstance(t[1], GammaEqualize):
+            photometric, t = {"op": "gamma_equalize", "target": t[1].target}, t[2:]
         elif len(t) == 3 and isinstance(t[0], Pil2Numpy):
             t = t[1:]
         if len(t) == 2 and isinstance(t[0], ToTensor) and isinstance(t[1], Normalize) and len(t[1].mean) == 3 \
                 and t[1].strict_shape:
-            return (list(t[1].mean), list(t[1].std), clahe) if clahe else (list(t[1].mean), list(t[1].std))
+            return (list(t[1].mean), list(t[1].std), photometric) if photometric else (list(t[1].mean), list(t[1].std))
         return None
 
 
@@ -314,15 +403,25 @@ class ToUint8HWC:
         return torch.from_numpy(np.array(pic.convert("RGB")))
 
 
-TRANSFORMS = {"totensor": ToTensor, "normalize": Normalize, "pil2np": Pil2Numpy, "apply_clahe": ApplyClahe}
+TRANSFORMS = {"totensor": ToTensor, "normalize": Normalize, "pil2np": Pil2Numpy, "apply_clahe": ApplyClahe,
+              "match_histogram": MatchHistogram, "gamma_equalize": GammaEqualize}
 
 
 def device_convert(tail):
     """The device half of a transform chain ``Compose.device_tail()`` recognised: uint8 ``[B,H,W,3]`` -> normalised fp32
-    ``[B,3,H,W]`` (``mdx_u8_to_chw``, or ``mdx_clahe_u8_to_chw`` for the CLAHE networks' chain)."""
+    ``[B,3,H,W]`` (``mdx_u8_to_chw``; with a third element ``mdx_clahe_u8_to_chw`` for the CLAHE networks' chain, or what its
+    ``"op"`` names: ``mdx_histmatch_u8_to_chw``, ``mdx_gamma_u8_to_chw``)."""
     from . import ops
     if len(tail) > 2 and tail[2]:
-        return lambda u8: ops.clahe_u8_to_chw(u8, tail[2]["clip_limit"], tail[2]["grid"], tail[0], tail[1])
+        par = tail[2]
+        op = par.get("op", "apply_clahe")
+        if op == "apply_clahe":
+            return lambda u8: ops.clahe_u8_to_chw(u8, par["clip_limit"], par["grid"], tail[0], tail[1])
+        if op == "match_histogram":
+            return lambda u8: ops.histmatch_u8_to_chw(u8, tail[0], tail[1], par["cdf"](u8.device) if par["cdf"] else None)
+        if op == "gamma_equalize":
+            return lambda u8: ops.gamma_u8_to_chw(u8, par["target"], tail[0], tail[1])
+        raise KeyError("device_convert: no device operator %r" % (op,))
     return lambda u8: ops.u8_to_chw(u8, tail[0], tail[1])
 
 

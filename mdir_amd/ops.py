@@ -297,6 +297,75 @@ def clahe_u8_to_chw(images, clip_limit, grid, mean, std, return_intermediates=Fa
     return out
 
 
+def _photometric_args(images, mean, std, who):
+    if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4
+            and images.is_contiguous() and images.shape[3] == 3):
+        raise ValueError("%s expects a contiguous uint8 [B,H,W,3] CUDA/ROCm tensor (no CPU fallback)" % who)
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean / std need 3 values")
+    b, h, w, _ = images.shape
+    arr = ctypes.c_float * 3
+    return b, h, w, arr(*[float(v) for v in mean]), arr(*[float(v) for v in std])
+
+
+def _photometric_regions(ws, b, h, w):
+    """Views of the workspace regions of include/mdx_photometric.h: x, x' (or log2 x), counts, fp, gamma, solver info."""
+    n = b * h * w
+    plane = -(-(4 * n) // 256) * 256
+    small = -(-(8 * b) // 256) * 256
+    at = 4 * plane
+    return (ws[:4 * n].view(torch.float32).view(b, h, w), ws[plane:plane + 4 * n].view(torch.float32).view(b, h, w),
+            ws[at:at + 1024 * b].view(torch.int32).view(b, 256), ws[at + 1024 * b:at + 3072 * b].view(torch.float64).view(b, 256),
+            ws[at + 3072 * b:at + 3072 * b + 8 * b].view(torch.float64),
+            ws[at + 3072 * b + small:at + 3072 * b + small + 8 * b].view(torch.int32).view(b, 2))
+
+
+def histmatch_u8_to_chw(images, mean, std, target_cdf=None, return_intermediates=False):
+    """uint8 RGB ``[B,H,W,3]`` device images -> histogram matching of the Lab lightness -> normalised fp32 ``[B,3,H,W]``
+    (``mdx_histmatch_u8_to_chw``): the scenarios' ``pil2np | match_histogram:<eq or name> | totensor | normalize``.
+    ``target_cdf``: None for ``eq`` (global histogram equalisation), or a float64 device tensor of the 256 cumulative values of the
+    target histogram (``datasets.register_histogram``).  ``return_intermediates``: also the lightness ``[B,H,W]`` f32, the counts
+    ``[B,256]`` int32, the table ``fp`` ``[B,256]`` f64 and the mapped lightness ``[B,H,W]`` f32 the kernels left in the workspace."""
+    b, h, w, mean_c, std_c = _photometric_args(images, mean, std, "histmatch_u8_to_chw")
+    cdf_p = None
+    if target_cdf is not None:
+        cdf_p = _dev(target_cdf, torch.float64, "target_cdf")
+        if target_cdf.numel() != 256 or target_cdf.device != images.device:
+            raise ValueError("target_cdf must hold 256 values on the images' device")
+    out = torch.empty((b, 3, h, w), dtype=torch.float32, device=images.device)
+    ws = _workspace(_lib.lib().mdx_photometric_workspace(b, h, w), images.device)
+    if images.numel():
+        with _on(images):
+            check(_lib.lib().mdx_histmatch_u8_to_chw(images.data_ptr(), b, h, w, cdf_p, mean_c, std_c, ws.data_ptr(), ws.numel(),
+                                                     out.data_ptr(), _stream()), "mdx_histmatch_u8_to_chw")
+    if return_intermediates:
+        x, mapped, counts, fp, _, _ = _photometric_regions(ws, b, h, w)
+        return out, x, counts, fp, mapped
+    return out
+
+
+def gamma_u8_to_chw(images, target, mean, std, return_intermediates=False):
+    """uint8 RGB ``[B,H,W,3]`` device images -> gamma equalisation of the Lab lightness (per image the gamma in [0.1, 10] with
+    ``mean(x ** gamma) = target``) -> normalised fp32 ``[B,3,H,W]`` (``mdx_gamma_u8_to_chw``): the scenarios'
+    ``pil2np | gamma_equalize:<target> | totensor | normalize``.  ``return_intermediates``: also the lightness ``[B,H,W]`` f32 and
+    gamma ``[B]`` f64 the kernels left in the workspace; ``return_intermediates="solver"``: after them int32 ``[B,2]``, the secant
+    steps taken and 1 where the fallback decided."""
+    b, h, w, mean_c, std_c = _photometric_args(images, mean, std, "gamma_u8_to_chw")
+    target = float(target)
+    if not 0.0 < target < 1.0:
+        raise ValueError("gamma_u8_to_chw: target %r must satisfy 0 < target < 1" % (target,))
+    out = torch.empty((b, 3, h, w), dtype=torch.float32, device=images.device)
+    ws = _workspace(_lib.lib().mdx_photometric_workspace(b, h, w), images.device)
+    if images.numel():
+        with _on(images):
+            check(_lib.lib().mdx_gamma_u8_to_chw(images.data_ptr(), b, h, w, target, mean_c, std_c, ws.data_ptr(), ws.numel(),
+                                                 out.data_ptr(), _stream()), "mdx_gamma_u8_to_chw")
+    if return_intermediates:
+        x, _, _, _, gamma, info = _photometric_regions(ws, b, h, w)
+        return (out, x, gamma, info) if return_intermediates == "solver" else (out, x, gamma)
+    return out
+
+
 def bilinear_pyramid(x, scales):
     """``[F.interpolate(x, scale_factor=s, mode="bilinear", align_corners=False) for s in scales]`` for an fp32
     ``[B,C,H,W]`` device tensor, all levels in ONE launch (``mdx_bilinear_pyramid``); a scale of exactly 1 returns ``x``."""
