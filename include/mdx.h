@@ -961,6 +961,16 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * tests/test_gpu_photometric_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_photometric.h"
 
+/* --------------------------------------------------------------- trainable tail */
+
+/* What a gradient step on mined tuples needs after the trunk: the backward of the global pooling (GeM with the gradient of its
+ * exponent, MAC, SPoC) and of the row L2 normalisation, and the reference's contrastive and triplet losses with their gradients.  The
+ * whole contract -- the formulas, the layout of a tuple batch, the summation orders, the launches, the refusals -- is stated in
+ * mdx_train.h, beside this file, with the prototypes; their names are in _lib.TRAIN_EXPORTS, for the reason given above for
+ * mdx_knn_join.h, and their census is tests/test_train_host.py (every prototype is exported and bound; the four launching ones have
+ * cases in tests/test_gpu_train_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_train.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

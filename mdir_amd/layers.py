@@ -6,7 +6,12 @@ Drop-in for ``mdir/external/cirtorch/layers/{functional,pooling,normalization}.p
 arithmetic runs in the HIP library (``mdx_pool_l2n`` / ``mdx_l2n_rows``); there is
 no torch-op or CPU fallback.  ``rmac`` / ``RMAC`` (functional.py:26-72, pooling.py:50-60; round 5) complete the
 ``POOLING`` registry of imageretrievalnet.py:32-37, ``roipool`` / ``Rpool`` (functional.py:75-121, pooling.py:62-95; round 5)
-the ``regional: True`` networks; the losses are out of scope.
+the ``regional: True`` networks.
+
+Under autograd -- ``torch.is_grad_enabled()`` and the map (or, for ``gem`` and the network's fused tail, ``p``) requires a gradient --
+``gem`` / ``mac`` / ``spoc`` / ``l2n`` and their modules go through ``mdir_amd.autograd`` (the same forward bits, a HIP backward);
+R-MAC and the regional pooling have no backward and say so.  ``contrastive_loss`` / ``triplet_loss`` (functional.py:141-173) are the
+functional forms of ``mdir_amd.criterion``.
 """
 import functools
 import math
@@ -15,16 +20,25 @@ import torch
 import torch.nn as nn
 from torch.nn.parameter import Parameter
 
-from . import ops
+from . import autograd, ops
 
 
 def _as_scalar(p):
     return float(p.detach().reshape(-1)[0]) if isinstance(p, torch.Tensor) else float(p)
 
 
-def _pool(x, kind, p=3.0, eps=1e-6):
-    out = ops.pool_l2n(x.contiguous(), kind, p, eps, l2n_eps=None)
+def _pool(x, kind, p=3.0, eps=1e-6, p_tensor=None):
+    """``p_tensor``: the exponent as a tensor that may ask for its gradient (``p`` is then its value)."""
+    if autograd.wanted(x, p_tensor):
+        out = autograd.PoolL2N.apply(x, p_tensor if kind == "gem" else None, kind, eps, None)
+    else:
+        out = ops.pool_l2n(x.contiguous(), kind, p, eps, l2n_eps=None)
     return out.reshape(x.shape[0], x.shape[1], 1, 1)
+
+
+def _no_backward(x, what):
+    if autograd.wanted(x):
+        raise NotImplementedError("%s has no backward: train with the global poolings gem, mac or spoc (not regional, no local whitening)" % what)
 
 
 def mac(x):
@@ -36,7 +50,7 @@ def spoc(x):
 
 
 def gem(x, p=3, eps=1e-6):
-    return _pool(x, "gem", _as_scalar(p), eps)
+    return _pool(x, "gem", _as_scalar(p), eps, p if isinstance(p, torch.Tensor) else None)
 
 
 @functools.lru_cache(maxsize=256)
@@ -69,15 +83,18 @@ def rmac_regions(H, W, L=3):
 
 def rmac(x, L=3, eps=1e-6):
     """R-MAC (functional.py:26-72): ``[B,C,H,W] -> [B,C,1,1]``, NOT normalised as a whole (``self.norm`` follows in the network)."""
+    _no_backward(x, "rmac")
     return ops.rmac(x.contiguous(), rmac_regions(int(x.shape[2]), int(x.shape[3]), int(L)), eps).reshape(x.shape[0], x.shape[1], 1, 1)
 
 
 def l2n(x, eps=1e-6):
     """``x / (||x||_2 over dim 1 + eps)``; any trailing singleton dims are kept."""
     shape = x.shape
-    flat = x.reshape(shape[0], -1).clone() if x.dim() > 1 else x.reshape(1, -1).clone()
     if x.dim() > 2 and any(s != 1 for s in shape[2:]):
         raise ValueError("l2n on the MI355X path expects [B,D] or [B,D,1,1] (global descriptors)")
+    if autograd.wanted(x):
+        return autograd.L2NRows.apply(x.reshape(shape[0], -1) if x.dim() > 1 else x.reshape(1, -1), None, eps).reshape(shape)
+    flat = x.reshape(shape[0], -1).clone() if x.dim() > 1 else x.reshape(1, -1).clone()
     return ops.l2n_rows_(flat.contiguous(), eps=eps).reshape(shape)
 
 
@@ -115,7 +132,9 @@ class GeM(nn.Module):
         return self._p_cache[1]
 
     def forward(self, x):
-        return _pool(x, "gem", self.p_value(), self.eps)
+        # (a map that asks for no gradient keeps the plain route even though ``p`` is a Parameter: a bare ``GeM()(x)`` outside
+        # ``no_grad`` has always returned a plain tensor; inside ImageRetrievalNet the fused tail also follows ``p``)
+        return _pool(x, "gem", self.p_value(), self.eps, self.p if autograd.wanted(x) else None)
 
     def __repr__(self):
         return self.__class__.__name__ + "(p={:.4f}, eps={})".format(self.p.data.tolist()[0], self.eps)
@@ -139,6 +158,7 @@ class RMAC(nn.Module):
 def roipool(x, rpool, L=3, eps=1e-6):
     """``[B,C,H,W] -> [B,R,C,1,1]``: ``rpool`` of the whole map and of every R-MAC region (functional.py:75-121).  One launch
     for the poolings the library knows (``mdx_roipool``); a foreign module is called region by region, as the reference does."""
+    _no_backward(x, "roipool / Rpool (regional pooling)")
     regions = rmac_regions(int(x.shape[2]), int(x.shape[3]), int(L))
     kind = pool_kind(rpool)
     if kind is not None:
@@ -197,6 +217,18 @@ class L2N(nn.Module):
 
     def __repr__(self):
         return self.__class__.__name__ + "(eps=" + str(self.eps) + ")"
+
+
+def contrastive_loss(x, label, margin=0.7, eps=1e-6):
+    """functional.py:141-157 on ``x`` [D,N]: ``mdx_contrastive_loss`` (loss and gradient in one call)."""
+    from .criterion import tuple_loss
+    return tuple_loss("contrastive", x, label, margin, eps)
+
+
+def triplet_loss(x, label, margin=0.1):
+    """functional.py:160-173 on ``x`` [D,N]: ``mdx_triplet_loss``."""
+    from .criterion import tuple_loss
+    return tuple_loss("triplet", x, label, margin)
 
 
 POOLING = {"mac": MAC, "spoc": SPoC, "gem": GeM, "rmac": RMAC}   # networks/imageretrievalnet.py:32-37

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import autograd, ops
 from .backbones import OUTPUT_DIM, TrunkSequential, build_features, check_precision
 from .datasets import ImagesFromList, ToUint8HWC, device_convert, get_data_root, make_loader
 from .graphs import ShapeGraphs, graphs_enabled, parallel_map
@@ -66,8 +66,26 @@ class ImageRetrievalNet(nn.Module):
             x = x.half()
         return self.features(x)
 
+    def _forward_grad(self, o):
+        """The tail under autograd (``mdir_amd.autograd``): the calls and the bits of ``forward``, with a backward.  The global
+        poolings and the in-network whitening only, on fp32 maps."""
+        if self.lwhiten is not None:
+            raise NotImplementedError("local whitening has no backward: train with local_whitening: False")
+        if o.dtype == torch.float16:
+            raise NotImplementedError("the fp16 trunk (precision: f16) has no backward: train with precision: f32")
+        kind = pool_kind(self.pool)
+        if kind is None:
+            raise NotImplementedError("%s has no backward: train with pooling gem, mac or spoc, regional: False" % type(self.pool).__name__)
+        p = self.pool.p if kind[0] == "gem" else None
+        o = autograd.PoolL2N.apply(o, p, kind[0], kind[2], self.norm.eps)
+        if self.whiten is not None:
+            o = autograd.WhitenLinear.apply(o, self.whiten.weight, self.whiten.bias, self._whiten_shard(), self.norm.eps)
+        return o.permute(1, 0)
+
     def forward(self, x):
         o = self.trunk(x)
+        if autograd.wanted(o, getattr(self.pool, "p", None), *(self.whiten.parameters() if self.whiten is not None else ())):
+            return self._forward_grad(o)
         if self.lwhiten is not None:   # local whitening: plain torch, not on the eval.py path
             o = o.float()              # (an extra the f16 mode leaves alone: it gets fp32 maps)
             s = o.size()

@@ -1532,6 +1532,84 @@ def krecip_rerank(half_sets, kth, k, k2, raw, expanded, scores, top_ids, lam, ou
     return out
 
 
+# ------------------------------------------------------------------ trainable tail (include/mdx_train.h)
+
+def pool_bwd(feat, pooled, grad_pooled, kind="gem", p=3.0, pool_eps=1e-6):
+    """Backward of the global pooling (``mdx_pool_bwd``): ``feat`` [B,C,H,W], ``pooled`` [B,C] (:func:`pool_l2n` with
+    ``l2n_eps=None``) and ``grad_pooled`` [B,C] -> ``(grad_feat [B,C,H,W], grad_p [1])``; ``grad_p`` is None for MAC / SPoC."""
+    fp = _dev(feat, torch.float32, "feature map")
+    if feat.dim() != 4:
+        raise ValueError("feature map must be [B,C,H,W]")
+    B, C, H, W = feat.shape
+    pp, gp = _dev(pooled, torch.float32, "pooled"), _dev(grad_pooled, torch.float32, "grad_pooled")
+    if pooled.numel() != B * C or grad_pooled.numel() != B * C:
+        raise ValueError("pool_bwd: pooled and grad_pooled must be [%d,%d], got %s and %s" % (B, C, tuple(pooled.shape), tuple(grad_pooled.shape)))
+    if kind not in POOL_KINDS:
+        raise ValueError("pool_bwd: unknown pooling kind %r, one of %s" % (kind, sorted(POOL_KINDS)))
+    grad_feat = torch.empty((B, C, H, W), dtype=torch.float32, device=feat.device)
+    h = _lib.lib()
+    grad_p = ws = None
+    if kind == "gem":
+        grad_p = torch.empty((1,), dtype=torch.float32, device=feat.device)
+        ws = _workspace(h.mdx_pool_bwd_workspace(B, C), feat.device)
+    with _on(feat):
+        check(h.mdx_pool_bwd(fp, pp, gp, B, C, H, W, POOL_KINDS[kind], float(p), float(pool_eps), _vp(grad_feat.data_ptr()),
+                             _vp(grad_p.data_ptr()) if grad_p is not None else None, _vp(ws.data_ptr()) if ws is not None else None,
+                             ws.numel() if ws is not None else 0, _stream()), "mdx_pool_bwd")
+    return grad_feat, grad_p
+
+
+def l2n_rows_bwd(x, grad_out, eps=1e-6):
+    """Backward of :func:`l2n_rows_` (``mdx_l2n_rows_bwd``): ``x`` [R,D] the rows BEFORE normalisation (bias added), ``grad_out``
+    [R,D] -> ``grad_x`` [R,D].  The bias' gradient is ``grad_x.sum(0)``, the caller's."""
+    xp, gp = _dev(x, torch.float32, "x"), _dev(grad_out, torch.float32, "grad_out")
+    if x.dim() != 2 or tuple(grad_out.shape) != tuple(x.shape):
+        raise ValueError("l2n_rows_bwd: x and grad_out must be [R,D], got %s and %s" % (tuple(x.shape), tuple(grad_out.shape)))
+    grad_x = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    with _on(x):
+        check(_lib.lib().mdx_l2n_rows_bwd(xp, gp, x.shape[0], x.shape[1], float(eps), _vp(grad_x.data_ptr()), _stream()), "mdx_l2n_rows_bwd")
+    return grad_x
+
+
+def _tuple_loss_args(x, label, nq, min_s, who):
+    xp, lp = _dev(x, torch.float32, "x"), _dev(label, torch.float32, "label")
+    if x.dim() != 2 or label.dim() != 1 or label.shape[0] != x.shape[1]:
+        raise ValueError("%s: x must be [D,N] and label [N], got %s and %s" % (who, tuple(x.shape), tuple(label.shape)))
+    d, n = x.shape
+    if isinstance(nq, bool) or not isinstance(nq, int) or nq < 1 or n % nq or n // nq < min_s:
+        raise ValueError("%s: N = %d columns are not nq = %r tuples of at least %d columns" % (who, n, nq, min_s))
+    return xp, lp, d, n
+
+
+def contrastive_loss(x, label, nq, margin=0.7, eps=1e-6):
+    """``LF.contrastive_loss`` and its gradient in one call (``mdx_contrastive_loss``): ``x`` [D,N], ``label`` fp32 [N] in the
+    layout of include/mdx_train.h (``nq`` tuples, the query first) -> ``(loss [1], grad_x [D,N])``.  The layout of ``label`` is the
+    caller's to check (:func:`mdir_amd.criterion.tuple_layout`)."""
+    xp, lp, d, n = _tuple_loss_args(x, label, nq, 2, "contrastive_loss")
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad_x = torch.empty((d, n), dtype=torch.float32, device=x.device)
+    h = _lib.lib()
+    ws = _workspace(h.mdx_tuple_loss_workspace(nq), x.device)
+    with _on(x):
+        check(h.mdx_contrastive_loss(xp, lp, d, n, nq, float(margin), float(eps), _vp(loss.data_ptr()), _vp(grad_x.data_ptr()),
+                                     _vp(ws.data_ptr()), ws.numel(), _stream()), "mdx_contrastive_loss")
+    return loss, grad_x
+
+
+def triplet_loss(x, label, nq, margin=0.1):
+    """``LF.triplet_loss`` and its gradient in one call (``mdx_triplet_loss``); arguments and results as :func:`contrastive_loss`,
+    tuples of at least three columns with one positive each."""
+    xp, lp, d, n = _tuple_loss_args(x, label, nq, 3, "triplet_loss")
+    loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+    grad_x = torch.empty((d, n), dtype=torch.float32, device=x.device)
+    h = _lib.lib()
+    ws = _workspace(h.mdx_tuple_loss_workspace(nq), x.device)
+    with _on(x):
+        check(h.mdx_triplet_loss(xp, lp, d, n, nq, float(margin), _vp(loss.data_ptr()), _vp(grad_x.data_ptr()), _vp(ws.data_ptr()),
+                                 ws.numel(), _stream()), "mdx_triplet_loss")
+    return loss, grad_x
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
