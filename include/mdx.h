@@ -971,6 +971,17 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * cases in tests/test_gpu_train_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_train.h"
 
+/* --------------------------------------------------------------- spherical k-means */
+
+/* Partitioning a database of L2-normalised descriptors by cosine similarity: beside mdx_scores_ex on an fp32 index of the centroids, an
+ * iteration needs the best centroid of every row of a score block (the first entry of mdx_topk, in one pass), the sum of every
+ * cluster's rows in a fixed order, and the normalisation of the sums.  The whole contract -- the tie rule, the segment chain that
+ * defines a sum to the bit, the order of the norm, the workspace layout, the launches, the refusals -- is stated in mdx_kmeans.h,
+ * beside this file, with the prototypes and MDX_KMEANS_SEGMENT; their names are in _lib.KMEANS_EXPORTS, for the reason given above for
+ * mdx_knn_join.h, and their census is tests/test_kmeans_host.py (every prototype is exported and bound; the three launching ones have
+ * cases in tests/test_gpu_kmeans_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_kmeans.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

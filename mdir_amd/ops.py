@@ -1610,6 +1610,107 @@ def triplet_loss(x, label, nq, margin=0.1):
     return loss, grad_x
 
 
+# ------------------------------------------------------------------ spherical k-means (include/mdx_kmeans.h)
+
+KMEANS_SEGMENT = 256              # include/mdx_kmeans.h MDX_KMEANS_SEGMENT: members per segment of the chain that defines a cluster's sum
+
+
+def _kmeans_tensor(t, dtype, who, what, dims):
+    """``t`` is a device tensor of ``dtype`` with ``dims`` dimensions, or a ValueError names it."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("%s: %s must be a CUDA/ROCm tensor: the MI355X path has no CPU fallback" % (who, what))
+    if t.dtype != dtype:
+        raise ValueError("%s: %s must be %s, got %s" % (who, what, dtype, t.dtype))
+    if t.dim() != dims or t.numel() < 1:
+        raise ValueError("%s: %s must be a non-empty %d-d tensor, got %s" % (who, what, dims, tuple(t.shape)))
+
+
+def _kmeans_matrix(t, who, what, strided=True):
+    """(pointer, row stride) of an fp32 device matrix with contiguous rows (``strided``: at any row stride)."""
+    _kmeans_tensor(t, torch.float32, who, what, 2)
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or not (strided or t.is_contiguous()):
+        raise ValueError("%s: %s must be %s" % (who, what, "a matrix with contiguous rows" if strided else "contiguous"))
+    return _vp(t.data_ptr()), (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def kmeans_argmax(scores, out_labels=None, out_best=None):
+    """``(labels int64 [m], best fp32 [m])``: per row of ``scores`` (fp32 ``[m, K]`` on the device, rows contiguous at any stride)
+    the first entry of :func:`topk` -- the larger score, equal scores by ascending id, ``-0 == +0``, NaN last -- in one pass
+    (``mdx_kmeans_argmax``).  ``out_labels`` / ``out_best``: a tensor to fill, None to allocate one, or False to leave that output
+    out (it comes back as None; not both)."""
+    who = "kmeans_argmax"
+    sp, ld = _kmeans_matrix(scores, who, "scores")
+    m, k = scores.shape
+    outs = []
+    for out, dtype, what in ((out_labels, torch.int64, "out_labels"), (out_best, torch.float32, "out_best")):
+        if out is False:
+            outs.append(None)
+            continue
+        if out is None:
+            out = torch.empty((m,), dtype=dtype, device=scores.device)
+        _kmeans_tensor(out, dtype, who, what, 1)
+        if out.shape[0] != m or not out.is_contiguous() or out.device != scores.device:
+            raise ValueError("%s: %s must be a contiguous [%d] tensor on %s, got %s on %s" % (who, what, m, scores.device, tuple(out.shape), out.device))
+        outs.append(out)
+    if outs[0] is None and outs[1] is None:
+        raise ValueError("%s: out_labels and out_best are both False: nothing to compute" % who)
+    with _on(scores):
+        check(_lib.lib().mdx_kmeans_argmax(sp, m, k, ld, _vp(outs[0].data_ptr()) if outs[0] is not None else None,
+                                           _vp(outs[1].data_ptr()) if outs[1] is not None else None, _stream()), "mdx_kmeans_argmax")
+    return outs[0], outs[1]
+
+
+def kmeans_sums(rows, members, offsets, k):
+    """fp32 ``[k, d]``: the sum of the rows of every cluster (``mdx_kmeans_sums``).  ``rows`` fp32 ``[n, d]`` on the device (rows
+    contiguous at any stride), ``members`` int64: the row ids grouped by cluster, ascending inside a cluster (at most ``n`` of them;
+    rows may be left out), ``offsets`` int64 ``[k + 1]``: cluster c owns ``members[offsets[c]:offsets[c + 1]]``.  Defined to the bit
+    by the segment chain of include/mdx_kmeans.h (``KMEANS_SEGMENT`` members per segment, tests/kmeans_restatement.py); an empty
+    cluster gets zeros, an id outside ``[0, n)`` is skipped."""
+    who = "kmeans_sums"
+    rp, ld = _kmeans_matrix(rows, who, "rows")
+    n, d = rows.shape
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("%s: k must be an integer >= 1, got %r" % (who, k))
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    if members.shape[0] > n or not members.is_contiguous() or members.device != rows.device:
+        raise ValueError("%s: members must be a contiguous tensor of at most n = %d ids on %s, got %s on %s"
+                         % (who, n, rows.device, tuple(members.shape), members.device))
+    if offsets.shape[0] != k + 1 or not offsets.is_contiguous() or offsets.device != rows.device:
+        raise ValueError("%s: offsets must be a contiguous [k + 1] = [%d] tensor on %s, got %s on %s"
+                         % (who, k + 1, rows.device, tuple(offsets.shape), offsets.device))
+    if members.shape[0] < n:                                   # the library clamps offsets to n: give it n entries to read
+        padded = torch.full((n,), -1, dtype=torch.int64, device=rows.device)
+        padded[:members.shape[0]] = members
+        members = padded
+    sums = torch.empty((k, d), dtype=torch.float32, device=rows.device)
+    h = _lib.lib()
+    ws = _workspace(h.mdx_kmeans_sums_workspace(n, k, d), rows.device)
+    with _on(rows):
+        check(h.mdx_kmeans_sums(rp, n, d, ld, _vp(members.data_ptr()), _vp(offsets.data_ptr()), k, _vp(sums.data_ptr()), _vp(ws.data_ptr()),
+                                ws.numel(), _stream()), "mdx_kmeans_sums")
+    return sums
+
+
+def kmeans_finish(sums, eps=1e-6, previous=None):
+    """fp32 ``[k, d]``: every row of ``sums`` divided by its norm plus ``eps`` (``mdx_kmeans_finish``; the L2N rule of
+    :func:`l2n_rows_`); a row of zeros becomes the same row of ``previous`` (fp32 ``[k, d]``), or stays zero without one."""
+    who = "kmeans_finish"
+    sp, _ = _kmeans_matrix(sums, who, "sums", strided=False)
+    k, d = sums.shape
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not eps >= 0 or math.isinf(eps):
+        raise ValueError("%s: eps must be a finite number >= 0, got %r" % (who, eps))
+    pp = None
+    if previous is not None:
+        pp, _ = _kmeans_matrix(previous, who, "previous", strided=False)
+        if tuple(previous.shape) != (k, d) or previous.device != sums.device:
+            raise ValueError("%s: previous must be [%d,%d] on %s, got %s on %s" % (who, k, d, sums.device, tuple(previous.shape), previous.device))
+    out = torch.empty((k, d), dtype=torch.float32, device=sums.device)
+    with _on(sums):
+        check(_lib.lib().mdx_kmeans_finish(sp, k, d, float(eps), pp, _vp(out.data_ptr()), _stream()), "mdx_kmeans_finish")
+    return out
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
