@@ -28,10 +28,6 @@ int probe_lds_order(hipStream_t s);
         }                                         \
     } while (0)
 
-// the alignment half alone (mdx_index.hip writes its size test out)
-#define MDX_CHECK_WORKSPACE_ALIGNED(ws, who) \
-    MDX_CHECK_ARG((((uintptr_t)(ws)) & 15) == 0, "%s: workspace must be 16-byte aligned", who)
-
 // every workspace of the ABI: `need` bytes (MDX_ERR_WORKSPACE otherwise, for NULL too) and 16-byte aligned (include/mdx.h,
 // "Alignment"; the carved pieces hold 8- and 16-byte words).  who: the entry point, a literal or a runtime string
 #define MDX_CHECK_WORKSPACE(who, ws, bytes, need)                                                                      \
@@ -40,7 +36,7 @@ int probe_lds_order(hipStream_t s);
             ::mdx::set_error("%s: workspace %lld B < required %lld B", who, (long long)(bytes), (long long)(need));    \
             return MDX_ERR_WORKSPACE;                                                                                  \
         }                                                                                                              \
-        MDX_CHECK_WORKSPACE_ALIGNED(ws, who);                                                                          \
+        MDX_CHECK_ARG((((uintptr_t)(ws)) & 15) == 0, "%s: workspace must be 16-byte aligned", who);                    \
     } while (0)
 
 #define MDX_HIP(call)                                                                   \

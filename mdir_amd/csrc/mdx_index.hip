@@ -13,11 +13,14 @@
 // score is the k = 0..D-1 fused-multiply-add chain stated in oracle/chain.c.
 #include <stdarg.h>
 
+#include <type_traits>
+
 #include "mdx_common.h"
 #include "mdx_scores_kernel.h"
 #include "mdx_scores_split_kernel.h"
 #include "mdx_scores_stream_kernel.h"
 #include "mdx_scores_i8_kernel.h"
+#include "mdx_retile_kernel.h"
 
 namespace mdx {
 
@@ -32,250 +35,102 @@ void set_error(const char *fmt, ...)
 }
 
 // ---------------------------------------------------------------------------
-// Re-tiling: an fp32 matrix [rows, k] in either layout of the API -> fragment-order tiles (the index build, the queries
-// of every call, the whitening matrix).  Rows >= n and k >= d read 0; `center[k]` (or nothing) is subtracted on the way.
-//   fp32 tile = 16 rows x 16 k: lane (g, j), element t = (row j, k 16 kb + 4 t + g)
-//   fp16 tile = 16 rows x 32 k: lane (g, j), element e = (row j, k 32 kb + 8 g + e), round-to-nearest-even
-// Round 1-3 let every lane fetch its own elements from the source: a wave-load was 16 pieces of 16 B (row-major sources)
-// or 4 pieces of 64 B (dimension-major) -- the build of the 8.2 GB shard ran at 0.86 TB/s read + write (19 ms; rocprofv3,
-// profiles/r04_summary.md).  Here a workgroup reads a block of the source in whole 1-KiB runs (64 lanes x 16 B along the
-// contiguous direction), parks it in LDS and every wave assembles tiles from there; the row stride of the LDS block makes the
-// 64 lanes of an assembling read hit 64 different banks.  The tiles leave as before, one coalesced KiB per wave-store.
-//   ROWMAJOR  (element (row, k) at src[row * d + k]):  block = 16 rows x 256 k
-//   otherwise (element (row, k) at src[k * n + row]):  block = 32 k x 256 rows (two fp32 k blocks or one fp16 k block)
+// The launch plan of a similarity call: which kernel instantiation a group of queries takes, and how nq queries are cut
+// into groups.  Everything below is host code; the kernels are in the *_kernel.h files.
 // ---------------------------------------------------------------------------
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));     // a 16-byte load at dword alignment (any n, d)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <bool F16, bool ROWMAJOR>
-__global__ __launch_bounds__(256) void retile_block_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ center,
-                                                           f32x4 *__restrict__ tiles, int64_t RT, int64_t KB, uint32_t *__restrict__ absmax,
-                                                           unsigned inner)
-{
-    // block id -> (bx, by) = (row tile, k span) or (row span, k block); the index that walks ALONG the source's contiguous
-    // direction is the fast one: consecutive blocks read adjacent KiB of the same lines
-    const unsigned bx = ROWMAJOR ? blockIdx.x / inner : blockIdx.x % inner, by = ROWMAJOR ? blockIdx.x % inner : blockIdx.x / inner;
-    constexpr int TK = F16 ? 32 : 16;                       // k per tile
-    constexpr int KBS = (!ROWMAJOR && !F16) ? 2 : 1;        // dimension-major fp32: two k blocks per block, so that a row tile's two tiles leave as one 2-KiB run
-    constexpr int LINES = ROWMAJOR ? 16 : TK * KBS;         // 1-KiB runs of the source per block: rows, or k rows
-    constexpr int LD = ROWMAJOR ? 260 : (F16 ? 258 : 272);  // floats per line in LDS (bank spread of the assembling reads)
-    __shared__ __attribute__((aligned(16))) float blk[LINES * LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, g = lane >> 4;
-    uint32_t best = 0;
-    // ---- the block, in runs of 1 KiB: line `l`, floats 4 * lane .. 4 * lane + 3
-    const int64_t line0 = ROWMAJOR ? (int64_t)bx * 16 : (int64_t)by * TK * KBS;      // first row / first k
-    const int64_t col0 = (ROWMAJOR ? (int64_t)by : (int64_t)bx) * 256 + 4 * lane;   // first k / first row of this lane
-    const int64_t nlines = ROWMAJOR ? n : d, ncols = ROWMAJOR ? d : n;
-    const int64_t ld_src = ncols;
-    float cen[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ROWMAJOR && center) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) cen[e] = col0 + e < d ? center[col0 + e] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < LINES / 4; ++i) {
-        const int l = wave * (LINES / 4) + i;
-        const int64_t line = line0 + l;
-        float x[4] = {0.f, 0.f, 0.f, 0.f};
-        if (line < nlines) {
-            const float *p = src + line * ld_src + col0;
-            if (col0 + 3 < ncols) {
-                const f32x4u v = *(const f32x4u *)p;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) x[e] = v[e];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) x[e] = col0 + e < ncols ? p[e] : 0.f;
-            }
-            if (center) {
-                const float ck = ROWMAJOR ? 0.f : center[line];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (col0 + e < ncols) x[e] -= ROWMAJOR ? cen[e] : ck;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t u = __float_as_uint(x[e]) & 0x7FFFFFFFu;
-            if (u < 0x7F800000u && u > best) best = u;
-        }
-        *(f32x2 *)&blk[l * LD + 4 * lane] = (f32x2){x[0], x[1]};
-        *(f32x2 *)&blk[l * LD + 4 * lane + 2] = (f32x2){x[2], x[3]};
-    }
-    __syncthreads();
-    // ---- tiles: 16 (fp16: 8) of them per block, 4 (2) per wave
-    constexpr int TILES = ROWMAJOR ? 256 / TK : 16 * KBS;       // dimension-major: tile tl = (row tile tl / KBS, k block tl % KBS)
-#pragma unroll
-    for (int i = 0; i < TILES / 4; ++i) {
-        const int tl = wave * (TILES / 4) + i;                          // tile of the block: along k (ROWMAJOR) or along rows
-        const int rl = ROWMAJOR ? 0 : tl / KBS, kl = ROWMAJOR ? 0 : tl % KBS;       // dimension-major: row tile and k block inside the block
-        const int64_t rt = ROWMAJOR ? (int64_t)bx : (int64_t)bx * 16 + rl;
-        const int64_t kb = ROWMAJOR ? (int64_t)by * TILES + tl : (int64_t)by * KBS + kl;
-        if (rt >= RT || kb >= KB) continue;
-        f32x4 out;
-        if constexpr (F16) {
-            f16x8 h;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) h[e] = (_Float16)(ROWMAJOR ? blk[j * LD + tl * 32 + 8 * g + e] : blk[(8 * g + e) * LD + rl * 16 + j]);
-            out = __builtin_bit_cast(f32x4, h);
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) out[t] = ROWMAJOR ? blk[j * LD + tl * 16 + 4 * t + g] : blk[(kl * 16 + 4 * t + g) * LD + rl * 16 + j];
-        }
-        tiles[(rt * KB + kb) * 64 + lane] = out;
-    }
-    if (absmax) {               // the shard's largest finite magnitude (index build only): the scale of MDX_F32_SPLIT2
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t other = (uint32_t)__shfl_xor((int)best, o, 64);
-            best = other > best ? other : best;
-        }
-        // one device-wide atomic per wave would be 2 M of them on ONE address for a 1 M x 2048 shard (~10 ns each: 20 of the
-        // build's 23 ms); a wave first looks at the cell -- a stale, smaller value only costs an atomic that changes nothing
-        if (lane == 0 && best > *(volatile uint32_t *)absmax) atomicMax(absmax, best);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// The int8 form of the re-tiling (MDX_I8, include/mdx.h states the quantisation).  A row's codes need its absmax first, so it
-// takes three launches: i8_absmax_kernel (a = max_k |x_k| per row, into the scale array), retile_i8_kernel (codes, reading a)
-// and i8_scale_kernel (a -> a / 127 in place).  mdx_quantize_i8 is the same three steps with row-major codes out.
-//   int8 tile = 16 rows x 64 k: lane (g, j), byte e = (row j, k 64 kb + 16 g + e)
-// ---------------------------------------------------------------------------
-constexpr int64_t I8_MAX_DPAD = 133120;        // largest multiple of 64 with 127^2 * d_pad < 2^31 (exact int32 accumulation)
-
-__device__ __forceinline__ float i8_inv(float a) { return __fdiv_rn(127.0f, a); }
-__device__ __forceinline__ float i8_scale(float a) { return __fdiv_rn(a, 127.0f); }
-__device__ __forceinline__ uint32_t i8_code(float x, float a, float inv)      // the code's byte
-{
-    if (a == 0.f) return 0u;
-    const float y = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.f), 127.f);
-    return (uint32_t)(uint8_t)(int8_t)(int)y;
-}
-// element (row, k) of the source, center[k] subtracted
-template <bool ROWMAJOR>
-__device__ __forceinline__ float i8_src(const float *src, int64_t n, int64_t d, const float *center, int64_t row, int64_t k)
-{
-    const float x = ROWMAJOR ? src[row * d + k] : src[k * n + row];
-    return center ? x - center[k] : x;
-}
-
-// a of rows 0 .. rows_pad-1 (0 for rows >= n).  Row-major: a wave per row; dimension-major: a thread per row (coalesced along rows)
-template <bool ROWMAJOR>
-__global__ __launch_bounds__(256) void i8_absmax_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ center,
-                                                        float *__restrict__ amax, int64_t rows_pad)
-{
-    if constexpr (ROWMAJOR) {
-        const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        const int lane = threadIdx.x & 63;
-        if (row >= rows_pad) return;
-        float m = 0.f;
-        if (row < n)
-            for (int64_t k = lane; k < d; k += 64) m = fmaxf(m, fabsf(i8_src<true>(src, n, d, center, row, k)));
-        m = wave_max(m);
-        if (lane == 0) amax[row] = m;
-    } else {
-        const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        if (row >= rows_pad) return;
-        float m = 0.f;
-        if (row < n)
-            for (int64_t k = 0; k < d; ++k) m = fmaxf(m, fabsf(i8_src<false>(src, n, d, center, row, k)));
-        amax[row] = m;
-    }
-}
-
-// one wave per tile (rt, kb) of RT x KB; every lane assembles its 16 bytes
-template <bool ROWMAJOR>
-__global__ __launch_bounds__(256) void retile_i8_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ center,
-                                                        const float *__restrict__ amax, i32x4 *__restrict__ tiles, int64_t RT, int64_t KB)
-{
-    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= RT * KB) return;
-    const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
-    const int64_t row = (tile / KB) * TILE_ROWS + j, k0 = (tile % KB) * 64 + 16 * g;
-    i32x4 w = {0, 0, 0, 0};
-    if (row < n) {
-        const float a = amax[row], inv = i8_inv(a);
-        float x[16];
-        if (ROWMAJOR && !center && k0 + 16 <= d) {
-            const f32x4u *p = (const f32x4u *)(src + row * d + k0);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const f32x4u t = p[v];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) x[4 * v + e] = t[e];
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) x[e] = k0 + e < d ? i8_src<ROWMAJOR>(src, n, d, center, row, k0 + e) : 0.f;
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) w[e >> 2] |= (int)(i8_code(x[e], a, inv) << (8 * (e & 3)));
-    }
-    tiles[tile * 64 + lane] = w;
-}
-
-__global__ __launch_bounds__(256) void i8_scale_kernel(float *__restrict__ amax, int64_t rows)
-{
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row < rows) amax[row] = i8_scale(amax[row]);
-}
-
-// mdx_quantize_i8: codes [n, d] row-major, one byte per thread (consecutive threads: consecutive k of a row)
-template <bool ROWMAJOR>
-__global__ __launch_bounds__(256) void quantize_i8_kernel(const float *__restrict__ src, int64_t n, int64_t d, const float *__restrict__ amax,
-                                                          int8_t *__restrict__ codes)
-{
-    const int64_t total = n * d;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int64_t row = e / d, k = e % d;
-        const float a = amax[row];
-        codes[e] = (int8_t)(uint8_t)i8_code(i8_src<ROWMAJOR>(src, n, d, nullptr, row, k), a, i8_inv(a));
-    }
-}
 
 // Loader/consumer kernel (4 MFMA waves + 4 LDS-DMA loader waves), chunks of 2 tiles along k,
 // ring of 3 stages.  R = 2 row tiles per consumer (128-row workgroups, (QT+8)*6 KiB of LDS)
 // for shards of >= 32 768 rows; R = 1 (64-row workgroups) below, so that small shards still
 // spread over the CUs -- measured crossover (round 2; the harness is in the history at commit 47a9fe2).
+constexpr int64_t R2_MIN_RT = 2048;            // row tiles from which R = 2 (fp32, fp16 and int8 shards, the row-major route)
 constexpr int LC_KC = 2, LC_NSTAGE = 3;
 #ifndef MDX_SCORES_PIPE_DEFAULT
 #define MDX_SCORES_PIPE_DEFAULT 1      // profiles/r05_scores_schedule.md: -1.0 ... -1.2 % (bit-equal); MDX_SCORES_PIPE=0 keeps the round-4 schedule
 #endif
 
-// > 64 KiB of dynamic LDS needs an opt-in per kernel and device: done once, not on every launch
-static int lds_opt_in(const void *kern, int lds, bool *done)
+// Split-precision launches (mdx_scores_split_kernel.h): 8 consumer waves x R row tiles + 4 loader waves, one workgroup
+// per CU, ring of 3 stages of (3 QT + 16 R) KiB.  Up to SPLIT_QT query tiles per workgroup; more queries = more passes (grid.y).
+// R = 2 (256-row workgroups) from 65 536 rows; below, 128-row workgroups, so that the shard still spreads over the CUs.
+constexpr int SPLIT_CW = 8, SPLIT_NSTAGE = 3, SPLIT_QT = 5;
+constexpr int64_t SPLIT_R2_MIN_RT = 4096;
+
+// f(std::integral_constant<int, N>) for N = qt, or MAX for every qt outside 1 .. MAX - 1: a run-time tile count as a template argument
+template <int MAX, typename F>
+static int with_qt(int qt, F &&f)
 {
+    if constexpr (MAX > 1) {
+        if (qt >= 1 && qt < MAX) return with_qt<MAX - 1>(qt, f);
+    }
+    return f(std::integral_constant<int, MAX>{});
+}
+
+// Launches Kern.  > 64 KiB of dynamic LDS needs an opt-in per kernel and device: done once (the flags are Kern's), not on every launch
+template <auto Kern, typename... Args>
+static int launch(dim3 grid, dim3 block, int lds, hipStream_t s, Args... args)
+{
+    static bool opted[64];
     int dev = 0;
     MDX_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !done[dev]) {
-        MDX_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        if (dev >= 0 && dev < 64) done[dev] = true;
+    if (dev < 0 || dev >= 64 || !opted[dev]) {
+        MDX_HIP(hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        if (dev >= 0 && dev < 64) opted[dev] = true;
     }
+    hipLaunchKernelGGL(Kern, grid, block, lds, s, args...);
     return MDX_OK;
 }
+
+// what the launches of one call share: the tiles (or, ld != 0, the row-major matrix read where it lies), their geometry, the stream
+struct Shard { const f32x4 *tiles; int64_t n, RT; int KB; hipStream_t s; int64_t ld; };
 
 // where a launch puts its scores: rows == nullptr: the plain [nq, n] matrix `out`; else query q's run goes to rows[q] + col0
 // (device array of nq row pointers: mdx_scores_p2p)
 struct Route { float *const *rows; int64_t col0; };
 
+// One launch's share of the queries: `passes` runs (grid.y) of `tiles` query tiles each, from query tile `first` of the call on
+struct QGroup {
+    int64_t first;      // first query tile
+    int tiles;          // query tiles per workgroup
+    int nq_valid;       // queries that exist in the passes * tiles tiles
+    int tail;           // of them, in the last tile: 1 .. 16
+    int passes;         // > 1: full groups of the same size behind each other (only the call's last tile can be partial)
+    int64_t q0() const { return first * TILE_ROWS; }
+};
+constexpr int64_t MAX_PASSES = 32768;          // grid.y < 65 536
+
+// Cuts nq queries into groups of at most max_qt query tiles and hands each to launch_one(const QGroup &): the full groups first --
+// pass_grid: up to MAX_PASSES of them per launch, so that many queries against a small database still fill the chip (20 000
+// rows are 313 workgroups per group); else one by one -- then the rest
+template <typename F>
+static int for_query_groups(int64_t nq, int max_qt, bool pass_grid, F &&launch_one)
+{
+    const int64_t QT_total = ceil_div(nq, TILE_ROWS), full = QT_total / max_qt, step = pass_grid ? MAX_PASSES : 1;
+    auto group = [&](int64_t first, int tiles, int64_t passes) -> int {
+        const int64_t room = passes * tiles * TILE_ROWS, left = nq - first * TILE_ROWS;
+        const int nq_valid = (int)(left < room ? left : room);
+        int rc = launch_one(QGroup{first, tiles, nq_valid, nq_valid - (int)(passes * tiles - 1) * TILE_ROWS, (int)passes});
+        if (rc != MDX_OK) return rc;
+        MDX_LAUNCH_CHECK();
+        return MDX_OK;
+    };
+    for (int64_t g0 = 0; g0 < full; g0 += step) {
+        int rc = group(g0 * max_qt, max_qt, (full - g0) < step ? (full - g0) : step);
+        if (rc != MDX_OK) return rc;
+    }
+    return full * max_qt < QT_total ? group(full * max_qt, (int)(QT_total - full * max_qt), 1) : MDX_OK;
+}
+
+// The ring kernel on fp32 or fp16 tiles (MM), QT full query tiles + QR leftover tiles (<= 8 queries on v_mfma_f32_4x4x1).  Three
+// forms of it: the routed epilogue, the pipelined consumer (PIPE, 128-row workgroups on fp32 tiles) and the plain one
 template <int QT, int R, typename MM, int QR = 0, bool RM = false>
-static int launch_scores_lc(const f32x4 *db, const f32x4 *qt, float *out, int64_t n, int64_t RT,
-                            int KB, int nq_valid, hipStream_t s, int passes = 1, int64_t ld = 0, Route route = Route{nullptr, 0})
+static int launch_scores_lc(const Shard &sh, const f32x4 *qt, float *out, int nq_valid, int passes, Route route)
 {
     constexpr int lds = LC_NSTAGE * (QT + QR + 4 * R) * LC_KC * 1024;
-    const int64_t blocks = ceil_div(RT, (int64_t)4 * R);
+    const dim3 grid((unsigned)ceil_div(sh.RT, (int64_t)4 * R), (unsigned)passes), block(512);
     if constexpr (MM::STEPS == 4 && !RM) {
-        if (route.rows) {           // routed epilogue (the shipped schedule of each shape: PIPE for 128-row workgroups)
-            auto kr = scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, false, (R == 2 ? 1 : 0), 4, true>;
-            static bool opted_r[64];
-            int rcr = lds_opt_in((const void *)kr, lds, opted_r);
-            if (rcr != MDX_OK) return rcr;
-            hipLaunchKernelGGL(kr, dim3((unsigned)blocks, (unsigned)passes), dim3(512), lds, s, db, qt, out, n, KB, nq_valid, ld, route.rows,
-                               route.col0);
-            return MDX_OK;
-        }
+        if (route.rows)             // routed epilogue (the shipped schedule of each shape: PIPE for 128-row workgroups)
+            return launch<scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, false, (R == 2 ? 1 : 0), 4, true>>(
+                grid, block, lds, sh.s, sh.tiles, qt, out, sh.n, sh.KB, nq_valid, sh.ld, route.rows, route.col0);
     }
     if (route.rows) {
         set_error("routed scores need an fp32 tiled shard");
@@ -284,23 +139,12 @@ static int launch_scores_lc(const f32x4 *db, const f32x4 *qt, float *out, int64_
     if constexpr (MM::STEPS == 4 && !RM && R == 2) {
         // the pipelined consumer (PIPE): MDX_SCORES_PIPE=0/1 picks the form per launch (A/B in one process: tools/chain_power_probe.py)
         const char *e = getenv("MDX_SCORES_PIPE");
-        if (e ? e[0] == '1' : MDX_SCORES_PIPE_DEFAULT) {
-            auto kp = scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, RM, 1>;
-            static bool opted_p[64];
-            int rcp = lds_opt_in((const void *)kp, lds, opted_p);
-            if (rcp != MDX_OK) return rcp;
-            hipLaunchKernelGGL(kp, dim3((unsigned)blocks, (unsigned)passes), dim3(512), lds, s, db, qt, out, n, KB, nq_valid, ld,
-                               (float *const *)nullptr, (int64_t)0);
-            return MDX_OK;
-        }
+        if (e ? e[0] == '1' : MDX_SCORES_PIPE_DEFAULT)
+            return launch<scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, RM, 1>>(
+                grid, block, lds, sh.s, sh.tiles, qt, out, sh.n, sh.KB, nq_valid, sh.ld, (float *const *)nullptr, (int64_t)0);
     }
-    auto kern = scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, RM>;   // 2 = non-temporal database stream
-    static bool opted[64];
-    int rc = lds_opt_in((const void *)kern, lds, opted);
-    if (rc != MDX_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(512), lds, s, db, qt, out, n, KB, nq_valid, ld,
-                       (float *const *)nullptr, (int64_t)0);
-    return MDX_OK;
+    return launch<scores_lc_kernel<QT, R, LC_KC, LC_NSTAGE, 2, MM, QR, 4, RM>>(      // 2 = non-temporal database stream
+        grid, block, lds, sh.s, sh.tiles, qt, out, sh.n, sh.KB, nq_valid, sh.ld, (float *const *)nullptr, (int64_t)0);
 }
 
 // fp16 shards whose k range is a whole number of four-chunk stages (d_pad % 128 == 0: every descriptor size of the path) take the
@@ -312,196 +156,69 @@ static bool f16_streams(int KB)
     return !ring_only && KB % STREAM_PF == 0;
 }
 
-template <int QT, int R>
-static int launch_f16_stream(const f32x4 *db, const f32x4 *qt, float *out, int64_t n, int64_t RT, int KB, int nq_valid, hipStream_t s, int passes)
+// the register-streaming kernels: fp16 tiles, or (I8) int8 tiles with the row scales of both sides
+template <int QT, int R, bool I8>
+static int launch_stream(const Shard &sh, const float *db_scale, const f32x4 *qt, const float *q_scale, float *out, int nq_valid, int passes)
 {
     constexpr int WGS = QT <= 5 ? 3 : 2;
-    auto kern = scores_f16_stream_kernel<QT, R, WGS>;
     constexpr int lds = stream_lds_bytes<QT, R>();
-    static bool opted[64];
-    int rc = lds_opt_in((const void *)kern, lds, opted);
-    if (rc != MDX_OK) return rc;
-    const int64_t blocks = ceil_div(RT, (int64_t)STREAM_CW * R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(STREAM_CW * 64), lds, s, db, qt, out, n, KB, nq_valid);
-    return MDX_OK;
+    const dim3 grid((unsigned)ceil_div(sh.RT, (int64_t)STREAM_CW * R), (unsigned)passes), block(STREAM_CW * 64);
+    if constexpr (I8)
+        return launch<scores_i8_stream_kernel<QT, R, WGS>>(grid, block, lds, sh.s, sh.tiles, db_scale, qt, q_scale, out, sh.n, sh.KB, nq_valid);
+    else
+        return launch<scores_f16_stream_kernel<QT, R, WGS>>(grid, block, lds, sh.s, sh.tiles, qt, out, sh.n, sh.KB, nq_valid);
 }
 
+// QT query tiles against an fp32 or fp16 shard, R row tiles per consumer wave
 template <int QT, int R>
-static int launch_i8_stream(const f32x4 *db, const float *db_scale, const f32x4 *qt, const float *q_scale, float *out, int64_t n, int64_t RT,
-                            int KB, int nq_valid, hipStream_t s, int passes)
+static int launch_tiles(bool f16, const Shard &sh, const f32x4 *q, float *out, int nq_valid, int passes, Route route)
 {
-    constexpr int WGS = QT <= 5 ? 3 : 2;
-    auto kern = scores_i8_stream_kernel<QT, R, WGS>;
-    constexpr int lds = stream_lds_bytes<QT, R>();
-    static bool opted[64];
-    int rc = lds_opt_in((const void *)kern, lds, opted);
-    if (rc != MDX_OK) return rc;
-    const int64_t blocks = ceil_div(RT, (int64_t)STREAM_CW * R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(STREAM_CW * 64), lds, s, db, db_scale, qt, q_scale, out, n, KB,
-                       nq_valid);
-    return MDX_OK;
+    if (!f16) return launch_scores_lc<QT, R, MmaF32>(sh, q, out, nq_valid, passes, route);
+    if (f16_streams(sh.KB) && !route.rows) return launch_stream<QT, R, false>(sh, nullptr, q, nullptr, out, nq_valid, passes);
+    return launch_scores_lc<QT, R, MmaF16>(sh, q, out, nq_valid, passes, route);
 }
 
-template <int QT>
-static int launch_i8_qt(bool r2, const f32x4 *db, const float *db_scale, const f32x4 *qt, const float *q_scale, float *out, int64_t n,
-                        int64_t RT, int KB, int nq_valid, hipStream_t s, int passes)
+// One query group against a tiled fp32 / fp16 shard (r2: 128-row workgroups).  leftover_mfma: a last tile of <= 8 queries goes to
+// v_mfma_f32_4x4x1 beside tiles - 1 full tiles on the 16x16x4 MFMA (fp32 shards with 128-row workgroups)
+static int launch_group(const QGroup &g, bool r2, bool f16, bool leftover_mfma, const Shard &sh, const f32x4 *q, float *out, Route route)
 {
-    return r2 ? launch_i8_stream<QT, 2>(db, db_scale, qt, q_scale, out, n, RT, KB, nq_valid, s, passes)
-              : launch_i8_stream<QT, 1>(db, db_scale, qt, q_scale, out, n, RT, KB, nq_valid, s, passes);
-}
-
-static int dispatch_i8(int qt, bool r2, const f32x4 *db, const float *db_scale, const f32x4 *q, const float *q_scale, float *out, int64_t n,
-                       int64_t RT, int KB, int nq_valid, hipStream_t s, int passes)
-{
-    switch (qt) {
-        case 1: return launch_i8_qt<1>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 2: return launch_i8_qt<2>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 3: return launch_i8_qt<3>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 4: return launch_i8_qt<4>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 5: return launch_i8_qt<5>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 6: return launch_i8_qt<6>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        case 7: return launch_i8_qt<7>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-        default: return launch_i8_qt<8>(r2, db, db_scale, q, q_scale, out, n, RT, KB, nq_valid, s, passes);
-    }
-}
-
-// mode bit0: R = 2 (else 1), bit1: fp16 shard
-template <int QT>
-static int launch_qt(int mode, const f32x4 *db, const f32x4 *q, float *out, int64_t n, int64_t RT,
-                     int KB, int nq_valid, hipStream_t s, int passes = 1, Route route = Route{nullptr, 0})
-{
-    switch (mode) {
-        case 0: return launch_scores_lc<QT, 1, MmaF32>(db, q, out, n, RT, KB, nq_valid, s, passes, 0, route);
-        case 1: return launch_scores_lc<QT, 2, MmaF32>(db, q, out, n, RT, KB, nq_valid, s, passes, 0, route);
-        case 2:
-            if (f16_streams(KB)) return launch_f16_stream<QT, 1>(db, q, out, n, RT, KB, nq_valid, s, passes);
-            return launch_scores_lc<QT, 1, MmaF16>(db, q, out, n, RT, KB, nq_valid, s, passes);
-        default:
-            if (f16_streams(KB)) return launch_f16_stream<QT, 2>(db, q, out, n, RT, KB, nq_valid, s, passes);
-            return launch_scores_lc<QT, 2, MmaF16>(db, q, out, n, RT, KB, nq_valid, s, passes);
-    }
-}
-
-// `qt` query tiles of which the last holds <= 8 queries: qt-1 full tiles on the 16x16x4 MFMA + the leftover
-// tile on v_mfma_f32_4x4x1 (fp32 shards with 128-row workgroups)
-static int dispatch_leftover(int qt, const f32x4 *db, const f32x4 *q, float *out, int64_t n, int64_t RT, int KB,
-                             int nq_valid, hipStream_t s, Route route = Route{nullptr, 0})
-{
-    switch (qt) {
-        case 2: return launch_scores_lc<1, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        case 3: return launch_scores_lc<2, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        case 4: return launch_scores_lc<3, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        case 5: return launch_scores_lc<4, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        case 6: return launch_scores_lc<5, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        case 7: return launch_scores_lc<6, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-        default: return launch_scores_lc<7, 2, MmaF32, 1>(db, q, out, n, RT, KB, nq_valid, s, 1, 0, route);
-    }
-}
-
-static int dispatch_qt(int qt, int mode, const f32x4 *db, const f32x4 *q, float *out, int64_t n,
-                       int64_t RT, int KB, int nq_valid, hipStream_t s, Route route = Route{nullptr, 0})
-{
-    switch (qt) {
-        case 1: return launch_qt<1>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 2: return launch_qt<2>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 3: return launch_qt<3>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 4: return launch_qt<4>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 5: return launch_qt<5>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 6: return launch_qt<6>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        case 7: return launch_qt<7>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-        default: return launch_qt<8>(mode, db, q, out, n, RT, KB, nq_valid, s, 1, route);
-    }
+    if (leftover_mfma && r2 && !f16 && g.passes == 1 && g.tiles >= 2 && g.tail <= 8)
+        return with_qt<MAX_QT - 1>(g.tiles - 1, [&](auto qt) {
+            return launch_scores_lc<decltype(qt)::value, 2, MmaF32, 1>(sh, q, out, g.nq_valid, 1, route);
+        });
+    return with_qt<MAX_QT>(g.tiles, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        return r2 ? launch_tiles<QT, 2>(f16, sh, q, out, g.nq_valid, g.passes, route) : launch_tiles<QT, 1>(f16, sh, q, out, g.nq_valid, g.passes, route);
+    });
 }
 
 // The same kernels on a row-major database read where it lies (RM = true; mdx_scores_rowmajor)
-template <int R>
-static int dispatch_rowmajor(int qt, bool leftover, const float *db, int64_t ld, const f32x4 *q, float *out, int64_t n, int64_t RT, int KB,
-                             int nq_valid, hipStream_t s)
+static int launch_group_rowmajor(const QGroup &g, bool r2, const Shard &sh, const f32x4 *q, float *out)
 {
-    const f32x4 *d4 = (const f32x4 *)db;
-    if constexpr (R == 2) {
-        if (leftover) {
-            switch (qt) {
-                case 2: return launch_scores_lc<1, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                case 3: return launch_scores_lc<2, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                case 4: return launch_scores_lc<3, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                case 5: return launch_scores_lc<4, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                case 6: return launch_scores_lc<5, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                case 7: return launch_scores_lc<6, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-                default: return launch_scores_lc<7, 2, MmaF32, 1, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-            }
-        }
-    }
-    switch (qt) {
-        case 1: return launch_scores_lc<1, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 2: return launch_scores_lc<2, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 3: return launch_scores_lc<3, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 4: return launch_scores_lc<4, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 5: return launch_scores_lc<5, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 6: return launch_scores_lc<6, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        case 7: return launch_scores_lc<7, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-        default: return launch_scores_lc<8, R, MmaF32, 0, true>(d4, q, out, n, RT, KB, nq_valid, s, 1, ld);
-    }
+    const Route plain{nullptr, 0};
+    if (r2 && g.tiles >= 2 && g.tail <= 8)
+        return with_qt<MAX_QT - 1>(g.tiles - 1, [&](auto qt) {
+            return launch_scores_lc<decltype(qt)::value, 2, MmaF32, 1, true>(sh, q, out, g.nq_valid, 1, plain);
+        });
+    return with_qt<MAX_QT>(g.tiles, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        return r2 ? launch_scores_lc<QT, 2, MmaF32, 0, true>(sh, q, out, g.nq_valid, 1, plain)
+                  : launch_scores_lc<QT, 1, MmaF32, 0, true>(sh, q, out, g.nq_valid, 1, plain);
+    });
 }
 
-// Split-precision launches (mdx_scores_split_kernel.h): 8 consumer waves x R row tiles + 4 loader waves, one workgroup
-// per CU, ring of 3 stages of (3 QT + 16 R) KiB.  Up to SPLIT_QT query tiles per workgroup; more queries = more passes (grid.y).
-constexpr int SPLIT_CW = 8, SPLIT_NSTAGE = 3, SPLIT_QT = 5;
-
-template <int QT, int R>
-static int launch_split3(const f32x4 *db, const u32x4 *qp, float *out, int64_t n, int64_t RT, int KB, int QT_total,
-                         int qt_first, int nq_valid, hipStream_t s, int passes)
+// the split-precision kernels: three bf16 pieces, or (TWO) two fp16 pieces with the block scales of both sides
+template <int QT, int R, bool TWO>
+static int launch_split(const QGroup &g, const Shard &sh, const u32x4 *qp, float *out, int QT_total, int nq, float db_scale, const uint32_t *q_cell)
 {
-    auto kern = scores_split3_kernel<QT, R, SPLIT_NSTAGE, SPLIT_CW>;
-    constexpr int lds = SPLIT_NSTAGE * (3 * QT + 2 * SPLIT_CW * R) * 1024;
-    static bool opted[64];
-    int rc = lds_opt_in((const void *)kern, lds, opted);
-    if (rc != MDX_OK) return rc;
-    const int64_t blocks = ceil_div(RT, (int64_t)SPLIT_CW * R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(SPLIT_CW * 64 + 256), lds, s, db, qp, out, n, KB,
-                       QT_total, qt_first, nq_valid);
-    return MDX_OK;
-}
-
-template <int R>
-static int dispatch_split3(int qt, const f32x4 *db, const u32x4 *qp, float *out, int64_t n, int64_t RT, int KB, int QT_total,
-                           int qt_first, int nq_valid, hipStream_t s, int passes)
-{
-    switch (qt) {
-        case 1: return launch_split3<1, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, s, passes);
-        case 2: return launch_split3<2, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, s, passes);
-        case 3: return launch_split3<3, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, s, passes);
-        case 4: return launch_split3<4, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, s, passes);
-        default: return launch_split3<5, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, s, passes);
-    }
-}
-
-template <int QT, int R>
-static int launch_split2(const f32x4 *db, const u32x4 *qp, float *out, int64_t n, int64_t RT, int KB, int QT_total, int qt_first,
-                         int nq_valid, float db_scale, const uint32_t *q_cell, hipStream_t s, int passes)
-{
-    auto kern = scores_split2_kernel<QT, R, SPLIT_NSTAGE, SPLIT_CW>;
-    constexpr int lds = SPLIT_NSTAGE * (2 * QT + 2 * SPLIT_CW * R) * 1024;
-    static bool opted[64];
-    int rc = lds_opt_in((const void *)kern, lds, opted);
-    if (rc != MDX_OK) return rc;
-    const int64_t blocks = ceil_div(RT, (int64_t)SPLIT_CW * R);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)passes), dim3(SPLIT_CW * 64 + 256), lds, s, db, qp, out, n, KB, QT_total,
-                       qt_first, nq_valid, db_scale, q_cell);
-    return MDX_OK;
-}
-
-template <int R>
-static int dispatch_split2(int qt, const f32x4 *db, const u32x4 *qp, float *out, int64_t n, int64_t RT, int KB, int QT_total, int qt_first,
-                           int nq_valid, float db_scale, const uint32_t *q_cell, hipStream_t s, int passes)
-{
-    switch (qt) {
-        case 1: return launch_split2<1, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, db_scale, q_cell, s, passes);
-        case 2: return launch_split2<2, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, db_scale, q_cell, s, passes);
-        case 3: return launch_split2<3, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, db_scale, q_cell, s, passes);
-        case 4: return launch_split2<4, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, db_scale, q_cell, s, passes);
-        default: return launch_split2<5, R>(db, qp, out, n, RT, KB, QT_total, qt_first, nq_valid, db_scale, q_cell, s, passes);
-    }
+    constexpr int lds = SPLIT_NSTAGE * ((TWO ? 2 : 3) * QT + 2 * SPLIT_CW * R) * 1024;
+    const dim3 grid((unsigned)ceil_div(sh.RT, (int64_t)SPLIT_CW * R), (unsigned)g.passes), block(SPLIT_CW * 64 + 256);
+    if constexpr (TWO)
+        return launch<scores_split2_kernel<QT, R, SPLIT_NSTAGE, SPLIT_CW>>(grid, block, lds, sh.s, sh.tiles, qp, out, sh.n, sh.KB, QT_total,
+                                                                          (int)g.first, nq, db_scale, q_cell);
+    else
+        return launch<scores_split3_kernel<QT, R, SPLIT_NSTAGE, SPLIT_CW>>(grid, block, lds, sh.s, sh.tiles, qp, out, sh.n, sh.KB, QT_total,
+                                                                          (int)g.first, nq);
 }
 
 }  // namespace mdx
@@ -769,87 +486,46 @@ static int scores_impl(const mdx_index *ix, const float *queries, int64_t nq, in
     MDX_CHECK_ARG(nq > 0, "mdx_scores: nq=%lld must be positive", (long long)nq);
     MDX_CHECK_ARG(qlayout == MDX_DIM_MAJOR || qlayout == MDX_ROW_MAJOR, "mdx_scores: qlayout %d",
                   qlayout);
-    const int64_t need = mdx_scores_workspace(nq, ix->d);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_scores: workspace %lld B < required %lld B", (long long)workspace_bytes,
-                  (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores");
-    hipStream_t s = (hipStream_t)stream;
+    MDX_CHECK_WORKSPACE("mdx_scores", workspace, workspace_bytes, mdx_scores_workspace(nq, ix->d));
+    const Shard sh{ix->tiles, ix->n, ix->RT, (int)ix->KB, (hipStream_t)stream, 0};
     f32x4 *qtiles = (f32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS);
+    const bool r2 = ix->RT >= R2_MIN_RT;              // >= 32 768 rows: 128-row workgroups
     if (ix->storage == MDX_I8) {
         // int8 query tiles (QT_total * KB KiB), then one scale per padded query: round_up(nq, 16) * (d_pad + 4) bytes <= need
         float *q_scale = (float *)((char *)workspace + QT_total * ix->KB * 1024);
-        int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, s, MDX_I8, nullptr, q_scale);
+        int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, sh.s, MDX_I8, nullptr, q_scale);
         if (rc != MDX_OK) return rc;
-        const bool r2 = ix->RT >= 2048;           // >= 32 768 rows: 128-row workgroups
-        const int64_t full_passes = QT_total / MAX_QT;
-        for (int64_t p0 = 0; p0 < full_passes; p0 += 32768) {        // grid.y < 65 536
-            const int passes = (int)((full_passes - p0) < 32768 ? (full_passes - p0) : 32768);
-            const int64_t q0 = p0 * MAX_QT * TILE_ROWS;
-            rc = dispatch_i8(MAX_QT, r2, ix->tiles, ix->scales, qtiles + p0 * MAX_QT * ix->KB * 64, q_scale + q0, scores + q0 * ix->n, ix->n,
-                             ix->RT, (int)ix->KB, (int)((int64_t)passes * MAX_QT * TILE_ROWS), s, passes);
-            if (rc != MDX_OK) return rc;
-            MDX_LAUNCH_CHECK();
-        }
-        const int64_t qt0 = full_passes * MAX_QT;
-        if (qt0 < QT_total) {
-            const int64_t q0 = qt0 * TILE_ROWS;
-            rc = dispatch_i8((int)(QT_total - qt0), r2, ix->tiles, ix->scales, qtiles + qt0 * ix->KB * 64, q_scale + q0, scores + q0 * ix->n,
-                             ix->n, ix->RT, (int)ix->KB, (int)(nq - q0), s, 1);
-            if (rc != MDX_OK) return rc;
-            MDX_LAUNCH_CHECK();
-        }
-        return MDX_OK;
+        return for_query_groups(nq, MAX_QT, true, [&](const QGroup &g) {
+            const f32x4 *qp = qtiles + g.first * ix->KB * 64;
+            const float *qs = q_scale + g.q0();
+            float *op = scores + g.q0() * ix->n;
+            return with_qt<MAX_QT>(g.tiles, [&](auto qt) {
+                constexpr int QT = decltype(qt)::value;
+                return r2 ? launch_stream<QT, 2, true>(sh, ix->scales, qp, qs, op, g.nq_valid, g.passes)
+                          : launch_stream<QT, 1, true>(sh, ix->scales, qp, qs, op, g.nq_valid, g.passes);
+            });
+        });
     }
-    int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, s, ix->storage);
+    int rc = retile(queries, nq, ix->d, qlayout, center, qtiles, QT_total, ix->KB, sh.s, ix->storage);
     if (rc != MDX_OK) return rc;
 
-    const bool small = ix->RT < 2048;                 // < 32 768 rows: 64-row workgroups
-    int64_t qt_begin = 0;
-    const int64_t full_passes = QT_total / MAX_QT;
     static const bool no_pass_grid = getenv("MDX_NO_PASS_GRID") != nullptr, no_query_split = getenv("MDX_NO_QUERY_SPLIT") != nullptr,
                       no_leftover = getenv("MDX_NO_LEFTOVER_MFMA") != nullptr;
-    if (full_passes > 1 && full_passes < 65536 && !no_pass_grid && !route.rows) {
-        // many queries: all full groups of MAX_QT query tiles in ONE launch (grid.y = group), so that a
-        // small database still fills the chip (20 000 rows are 313 workgroups per group)
-        const int mode = (small ? 0 : 1) | (ix->storage == MDX_F16 ? 2 : 0);
-        rc = launch_qt<MAX_QT>(mode, ix->tiles, qtiles, scores, ix->n, ix->RT, (int)ix->KB,
-                               (int)(full_passes * MAX_QT * TILE_ROWS), s, (int)full_passes);     // nq_valid = queries of the launch
-        if (rc != MDX_OK) return rc;
-        MDX_LAUNCH_CHECK();
-        qt_begin = full_passes * MAX_QT;
-    }
-    if (qt_begin == 0 && QT_total <= MAX_QT && QT_total > 1 && ix->storage == MDX_F32 && !no_query_split) {
+    if (!r2 && QT_total > 1 && QT_total <= MAX_QT && ceil_div(ix->RT, (int64_t)4) * QT_total <= 1024 && ix->storage == MDX_F32 &&
+        !no_query_split) {
         // few queries against a small shard (rOxford5k alone: 70 x 4 993): 64-row workgroups taking all
         // query tiles are only RT/4 = 79 workgroups, each a 5-tile-long MFMA chain.  Give every workgroup
         // ONE query tile instead (grid.y = tile): 5x the workgroups, a fifth of the chain each.
-        const int64_t blocks = ceil_div(ix->RT, (int64_t)4);
-        if (small && blocks * QT_total <= 1024) {
-            rc = launch_qt<1>(0, ix->tiles, qtiles, scores, ix->n, ix->RT, (int)ix->KB, (int)nq, s, (int)QT_total, route);
-            if (rc != MDX_OK) return rc;
-            MDX_LAUNCH_CHECK();
-            return MDX_OK;
-        }
-    }
-    for (int64_t qt0 = qt_begin; qt0 < QT_total; qt0 += MAX_QT) {
-        const int qt = (int)((QT_total - qt0) < MAX_QT ? (QT_total - qt0) : MAX_QT);
-        const int64_t q0 = qt0 * TILE_ROWS;
-        const int nq_valid = (int)((nq - q0) < qt * TILE_ROWS ? (nq - q0) : qt * TILE_ROWS);
-        const f32x4 *qp = qtiles + qt0 * ix->KB * 64;
-        float *op = route.rows ? nullptr : scores + q0 * ix->n;
-        const int mode = (small ? 0 : 1) | (ix->storage == MDX_F16 ? 2 : 0);
-        const int tail = nq_valid - (qt - 1) * TILE_ROWS;      // queries in the last tile of this launch
-        if (mode == 1 && qt >= 2 && tail <= 8 && !no_leftover)
-            rc = dispatch_leftover(qt, ix->tiles, qp, op, ix->n, ix->RT, (int)ix->KB, nq_valid, s, route);
-        else
-            rc = dispatch_qt(qt, mode, ix->tiles, qp, op, ix->n, ix->RT, (int)ix->KB, nq_valid, s, route);
+        rc = launch_scores_lc<1, 1, MmaF32>(sh, qtiles, scores, (int)nq, (int)QT_total, route);
         if (rc != MDX_OK) return rc;
         MDX_LAUNCH_CHECK();
+        return MDX_OK;
     }
-    return MDX_OK;
+    return for_query_groups(nq, MAX_QT, !no_pass_grid && !route.rows, [&](const QGroup &g) {
+        return launch_group(g, r2, ix->storage == MDX_F16, !no_leftover, sh, qtiles + g.first * ix->KB * 64,
+                            route.rows ? nullptr : scores + g.q0() * ix->n, route);
+    });
 }
 
 int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *queries, int64_t nq, int qlayout, const float *center,
@@ -862,31 +538,16 @@ int mdx_scores_rowmajor(const float *db, int64_t n, int64_t d, const float *quer
                   "mdx_scores_rowmajor: d=%lld must be a multiple of 4 (rows are read in pieces of four values) and the matrix 4-byte aligned; "
                   "build an index for other shapes", (long long)d);
     MDX_CHECK_ARG(qlayout == MDX_DIM_MAJOR || qlayout == MDX_ROW_MAJOR, "mdx_scores_rowmajor: qlayout %d", qlayout);
-    const int64_t need = mdx_scores_workspace(nq, d);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_scores_rowmajor: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores_rowmajor");
-    hipStream_t s = (hipStream_t)stream;
+    MDX_CHECK_WORKSPACE("mdx_scores_rowmajor", workspace, workspace_bytes, mdx_scores_workspace(nq, d));
     f32x4 *qtiles = (f32x4 *)workspace;
-    const int64_t QT_total = ceil_div(nq, TILE_ROWS), KB = round_up(d, 64) / TILE_K, RT = ceil_div(n, TILE_ROWS);
-    int rc = retile(queries, nq, d, qlayout, center, qtiles, QT_total, KB, s, MDX_F32);
+    const int64_t QT_total = ceil_div(nq, TILE_ROWS), KB = round_up(d, 64) / TILE_K;
+    const Shard sh{(const f32x4 *)db, n, ceil_div(n, TILE_ROWS), (int)KB, (hipStream_t)stream, d};
+    int rc = retile(queries, nq, d, qlayout, center, qtiles, QT_total, KB, sh.s, MDX_F32);
     if (rc != MDX_OK) return rc;
-    const bool small = RT < 2048;                     // < 32 768 rows: 64-row workgroups
-    for (int64_t qt0 = 0; qt0 < QT_total; qt0 += MAX_QT) {
-        const int qt = (int)((QT_total - qt0) < MAX_QT ? (QT_total - qt0) : MAX_QT);
-        const int64_t q0 = qt0 * TILE_ROWS;
-        const int nq_valid = (int)((nq - q0) < qt * TILE_ROWS ? (nq - q0) : qt * TILE_ROWS);
-        const int tail = nq_valid - (qt - 1) * TILE_ROWS;      // queries in the last tile of this launch
-        const f32x4 *qp = qtiles + qt0 * KB * 64;
-        float *op = scores + q0 * n;
-        if (small) rc = dispatch_rowmajor<1>(qt, false, db, d, qp, op, n, RT, (int)KB, nq_valid, s);
-        else       rc = dispatch_rowmajor<2>(qt, qt >= 2 && tail <= 8, db, d, qp, op, n, RT, (int)KB, nq_valid, s);
-        if (rc != MDX_OK) return rc;
-        MDX_LAUNCH_CHECK();
-    }
-    return MDX_OK;
+    const bool r2 = sh.RT >= R2_MIN_RT;               // >= 32 768 rows: 128-row workgroups
+    return for_query_groups(nq, MAX_QT, false, [&](const QGroup &g) {
+        return launch_group_rowmajor(g, r2, sh, qtiles + g.first * KB * 64, scores + g.q0() * n);
+    });
 }
 
 int64_t mdx_scores_workspace_ex(int64_t nq, int64_t d, int compute)
@@ -908,11 +569,7 @@ int mdx_scores_ex(const mdx_index *ix, const float *queries, int64_t nq, int qla
     MDX_CHECK_ARG(nq > 0 && nq < (1 << 20), "mdx_scores_ex: nq=%lld", (long long)nq);
     MDX_CHECK_ARG(qlayout == MDX_DIM_MAJOR || qlayout == MDX_ROW_MAJOR, "mdx_scores_ex: qlayout %d", qlayout);
     const int64_t need = mdx_scores_workspace_ex(nq, ix->d, compute);
-    if (!workspace || workspace_bytes < need) {
-        set_error("mdx_scores_ex: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return MDX_ERR_WORKSPACE;
-    }
-    MDX_CHECK_WORKSPACE_ALIGNED(workspace, "mdx_scores_ex");
+    MDX_CHECK_WORKSPACE("mdx_scores_ex", workspace, workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     u32x4 *qp = (u32x4 *)workspace;
     const int64_t QT_total = ceil_div(nq, TILE_ROWS), NC = ix->KB / 2;
@@ -933,22 +590,19 @@ int mdx_scores_ex(const mdx_index *ix, const float *queries, int64_t nq, int qla
                            center, qp, QT_total, NC);
     }
     MDX_LAUNCH_CHECK();
-    const bool small = ix->RT < 4096;                 // < 65 536 rows: 128-row workgroups, so that the shard still spreads over the CUs
-    const int64_t full = QT_total / SPLIT_QT, rem = QT_total % SPLIT_QT;
-    auto go = [&](int qt, int64_t qt_first, int passes) -> int {
-        if (two)
-            return small ? dispatch_split2<1>(qt, ix->tiles, qp, scores, ix->n, ix->RT, (int)ix->KB, (int)QT_total, (int)qt_first, (int)nq, db_scale, q_cell, s, passes)
-                         : dispatch_split2<2>(qt, ix->tiles, qp, scores, ix->n, ix->RT, (int)ix->KB, (int)QT_total, (int)qt_first, (int)nq, db_scale, q_cell, s, passes);
-        return small ? dispatch_split3<1>(qt, ix->tiles, qp, scores, ix->n, ix->RT, (int)ix->KB, (int)QT_total, (int)qt_first, (int)nq, s, passes)
-                     : dispatch_split3<2>(qt, ix->tiles, qp, scores, ix->n, ix->RT, (int)ix->KB, (int)QT_total, (int)qt_first, (int)nq, s, passes);
-    };
-    int rc = MDX_OK;
-    for (int64_t g0 = 0; g0 < full && rc == MDX_OK; g0 += 32768)        // grid.y < 65 536
-        rc = go(SPLIT_QT, g0 * SPLIT_QT, (int)((full - g0) < 32768 ? (full - g0) : 32768));
-    if (rc == MDX_OK && rem) rc = go((int)rem, full * SPLIT_QT, 1);
-    if (rc != MDX_OK) return rc;
-    MDX_LAUNCH_CHECK();
-    return MDX_OK;
+    const Shard sh{ix->tiles, ix->n, ix->RT, (int)ix->KB, s, 0};
+    const bool r2 = ix->RT >= SPLIT_R2_MIN_RT;
+    // the kernels find a group's pieces and scores themselves, from the call's pointers and the group's first tile
+    return for_query_groups(nq, SPLIT_QT, true, [&](const QGroup &g) {
+        return with_qt<SPLIT_QT>(g.tiles, [&](auto qt) {
+            constexpr int QT = decltype(qt)::value;
+            if (two)
+                return r2 ? launch_split<QT, 2, true>(g, sh, qp, scores, (int)QT_total, (int)nq, db_scale, q_cell)
+                          : launch_split<QT, 1, true>(g, sh, qp, scores, (int)QT_total, (int)nq, db_scale, q_cell);
+            return r2 ? launch_split<QT, 2, false>(g, sh, qp, scores, (int)QT_total, (int)nq, db_scale, q_cell)
+                      : launch_split<QT, 1, false>(g, sh, qp, scores, (int)QT_total, (int)nq, db_scale, q_cell);
+        });
+    });
 }
 
 }  // extern "C"

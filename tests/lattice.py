@@ -305,11 +305,12 @@ def split2_pieces(a32):
 # (n, d, nq).  Branches of mdir_amd/csrc/mdx_index.hip reached (RT = round_up(ceil(n / 16), 8) row tiles; QT = ceil(nq / 16)):
 #   RT < 2048 (n <= 32 640): 64-row workgroups (R = 1); above: 128-row workgroups (R = 2) -- 32 640 / 32 641 is the switch
 #   of an index, 32 752 / 32 753 that of the row-major route (its RT is not rounded up); the issue's 32 767 .. 32 895 lie above both
-#   fp32, R = 1, 1 < QT <= 8 and RT / 4 * QT <= 1024: one query tile per workgroup (launch_qt<1> with grid.y = QT); above
-#   that product (8192 / 8193 rows at QT = 8): dispatch_qt<QT>
-#   fp32, R = 2, QT >= 2 and <= 8 queries in the last tile: dispatch_leftover<QT - 1>; else dispatch_qt<QT>
-#   QT = 9: a launch of 8 tiles and one of 1; QT = 17: two full groups in ONE launch (grid.y = 2) and a launch of 1
-#   fp16: round_up(d, 64) % 128 == 0 -> register-streaming kernel, == 64 -> ring kernel; int8: dispatch_i8<QT>, R as above
+#   fp32, R = 1, 1 < QT <= 8 and RT / 4 * QT <= 1024: one query tile per workgroup (launch_scores_lc<1, 1> with grid.y = QT);
+#   above that product (8192 / 8193 rows at QT = 8): launch_group -> launch_tiles<QT, 1>
+#   fp32, R = 2, QT >= 2 and <= 8 queries in the last tile: launch_group takes launch_scores_lc<QT - 1, 2, MmaF32, 1> (the
+#   leftover tile); else launch_tiles<QT, 2>
+#   QT = 9: a launch of 8 tiles and one of 1; QT = 17: two full groups in ONE launch (grid.y = 2) and a launch of 1 (for_query_groups)
+#   fp16: round_up(d, 64) % 128 == 0 -> register-streaming kernel, == 64 -> ring kernel; int8: launch_stream<QT, R, true>, R as above
 #   split3 / split2: up to 5 query tiles per workgroup, more = passes; 128-row consumers below 65 536 rows (SPLIT_TRIPLES has the other)
 TRIPLES = [
     # 64-row workgroups, every tail of rows, queries and k

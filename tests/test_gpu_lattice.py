@@ -113,6 +113,23 @@ def test_unpipelined_consumer_on_the_common_grid(n, d, nq, monkeypatch):
     check_common(n, d, nq, storages=("f32",), extras=False)
 
 
+@pytest.mark.parametrize("storage", ["f32", "f16", "i8"])
+def test_partial_last_tile_behind_full_groups_stays_inside_the_scores(storage):
+    """250 queries are two full groups of eight query tiles whose last tile holds 10 queries.  One launch takes both groups
+    (grid.y = 2) and has to be told 250 queries, not the 256 its tiles have room for: the scores are the head of a larger
+    buffer here, and the six rows behind them keep their fill."""
+    from mdir_amd import ops
+    n, d, nq = 200, 64, 250
+    L = lattice.common(n, d, nq)
+    whole = torch.full((nq + 6, n), 7.0, dtype=torch.float32, device=DEV)
+    ix = ops.DescriptorIndex(dev(L.db), "ND", storage=storage)
+    try:
+        same(ix.scores(dev(L.queries), "ND", out=whole[:nq]), lattice.expected(L.qi, L.xi, 1.0), (storage, "250 queries"))
+    finally:
+        ix.close()
+    assert bool((whole[nq:] == 7.0).all())
+
+
 def _stream_shapes(triples):
     """The shapes whose fp16 shard takes the register-streaming kernel in-process (d_pad % 128 == 0): only there does
     MDX_F16_RING=1 change the kernel."""

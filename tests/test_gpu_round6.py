@@ -22,13 +22,15 @@ def dev(a):
 
 
 # ------------------------------------------------------------------------------------------------ direct-store exchange
-@pytest.mark.parametrize("shape", [(70001, 23, 256, 3), (40000, 70, 128, 4), (3000, 5, 64, 2)])
+@pytest.mark.parametrize("shape", [(70001, 23, 256, 3), (40000, 70, 128, 4), (3000, 5, 64, 2), (98400, 23, 64, 2), (98400, 32, 64, 2)])
 def test_p2p_ranks_in_one_process_equal_the_oracle(shape):
     """`mdx_scores_p2p` + `mdx_p2p_close_step` through ops.P2P with all ranks in this process (connected by pointers, one
     stream per rank): after a step every rank holds ITS queries' rows of the WHOLE score matrix -- bit for bit the chain
     oracle's -- and their ranking is `OC.rank_full`'s.  Three steps with other queries: the two receive buffers alternate and
-    the first step's view is overwritten by the third, not by the second.  Shapes: 128-row workgroups with the 4x4x1 leftover
-    tile (23 queries), 64-row workgroups with one query tile per workgroup (70 queries x 10 000-row shards), tiny shards.  (At most
+    the first step's view is overwritten by the third, not by the second.  Shapes: 64-row workgroups with one query tile per
+    workgroup (the first two: every chunk is below 32 768 rows) and with all tiles (tiny shards); 98 400 rows on two ranks are
+    chunks of 16 400 and 32 800 rows, the second on the routed 128-row workgroups: with the 4x4x1 leftover tile (23 queries: one
+    full tile + 7) and without (32 queries).  (At most
     four ranks here: ranks that live in ONE process are streams of one process, HIP multiplexes them onto four hardware queues, and a
     rank spinning for a peer's flag would hold the queue that peer's kernels wait in.  Rank PROCESSES have queues of their own: the
     rank-process cases below.)"""
