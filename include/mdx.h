@@ -982,6 +982,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * cases in tests/test_gpu_kmeans_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_kmeans.h"
 
+/* --------------------------------------------------------------- inverted file */
+
+/* Searching the partition that spherical k-means makes: a query is scored against the members of the lists whose centroids it scores
+ * best against, with the exact fp32 chain, and answered with the first k of them in mdx_rank_full's order.  Beside mdx_scores_ex and
+ * mdx_topk on an fp32 index of the centroids this takes a plan of the batch's probes (the inverted probe table), a list-major scan
+ * that reads a list's rows once for the queries that share it, and a selection per query.  The whole contract -- the layout of the
+ * plan, the candidate columns, the bounds that stand in for sizes the host does not know, the order, the refusals -- is stated in
+ * mdx_ivf.h, beside this file, with the prototypes, MDX_IVF_QUERY_GROUP and MDX_IVF_TILE; their names are in _lib.IVF_EXPORTS, for the
+ * reason given above for mdx_knn_join.h, and their census is tests/test_ivf_host.py (every prototype is exported and bound; the three
+ * launching ones have cases in tests/test_gpu_ivf_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_ivf.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -1,0 +1,189 @@
+"""An inverted file (IVF) over the partition of spherical k-means: score only the rows whose centroid is among a query's best.
+
+Every other search path of the library reads the whole database for every batch of queries; this one reads the lists a query probes.
+The partition is ``cluster.kmeans``'s (or any labels), the rows stay where they are, the scores are the exact fp32 chain, and the
+result is defined to the bit: with ``nprobe == lists`` it is ``ops.topk(index.scores(q), k)`` of an fp32 ``DescriptorIndex`` of the
+rows, with fewer probes it is that ranking restricted to the rows of the probed lists.  ``tests/ivf_restatement.py`` states it in numpy.
+
+``IVFIndex(rows, centroids, labels=None, chunk=None)``
+    ``rows`` fp32 ``[N, D]`` on the device, rows contiguous at any row stride (as ``ops.rescore`` accepts); read in place, never
+    copied or permuted.  ``centroids`` fp32 ``[K, D]`` on the same device, contiguous.  ``labels`` int64 ``[N]`` in ``[0, K)``: the
+    list of every row; ``None`` means ``cluster.assign(centroids, rows, chunk)[0]`` (``rows`` must then be contiguous).  Explicit
+    labels need not be the argmax: a row is found through the list it was put in.
+    The index keeps ``order``, ``offsets`` and ``sizes`` as ``cluster._members`` builds them -- a stable sort of the labels, so the
+    members of a list ascend -- and ``coarse``, an fp32 ``ops.DescriptorIndex`` of the centroids.  It reads ``sizes`` back once, at
+    build time (the one synchronisation a search rests on; the range check of explicit labels and the build of the coarse index
+    synchronise there too): from the sorted list sizes and tile counts it knows, for every ``nprobe``, the candidate
+    capacity of a query (``capacity(nprobe)``: the sum of the ``nprobe`` largest lists) and a bound on the scan's work items
+    (:func:`item_bound`), so a search reads nothing back.
+
+``IVFIndex.train(rows, lists, **kmeans_kwargs)``
+    ``cluster.kmeans(rows, lists, **kmeans_kwargs)``, then the index of ``fit.centroids`` and ``fit.labels``; the :data:`KMeans`
+    result stays reachable as ``.fit``.
+
+``index.search(queries, k, nprobe, qlayout="ND", center=None)`` -> :data:`IVFResult`
+    1. ``probes`` = the ids of ``ops.topk(coarse.scores(queries, qlayout, center=center), nprobe)``.  ``center`` has the library's
+       usual meaning, ``x_q = q - center`` in one fp32 subtraction, for the coarse stage and the scan alike.
+    2. ``ops.ivf_plan``: per query the first column of every probe's segment in its candidate row (a prefix sum of list sizes in
+       probe order) and ``scanned``, its number of candidates; per list the queries that probe it.
+    3. ``ops.ivf_scan``: list-major, a tile of 64 members of a list is read once for up to ``ops.IVF_QUERY_GROUP`` queries that probe
+       it.  ``scores`` are bit-identical to ``ops.DescriptorIndex(rows, "ND").scores(queries, qlayout, center)`` at the same id.
+    4. ``ops.ivf_select``: the first ``k`` candidates in ``rank_full``'s order: the larger score first, ``-0 == +0``, NaN last, equal
+       keys by ascending row id, whichever list a row sits in.  Where ``scanned[q] < k`` the tail is id ``-1`` and score NaN.
+    ``1 <= nprobe <= K`` and ``1 <= k <= ops.RESCORE_MAX_K``.  The queries are taken ``query_chunk(nprobe)`` at a time, so that the
+    candidate block stays under ``CANDIDATE_MEMORY_CAP`` bytes; the chunk changes no bit of the result.  Nothing is read back and
+    nothing synchronises.  There is no CPU fallback.
+
+``index.close()`` releases the coarse index.
+"""
+from collections import namedtuple
+
+import torch
+
+from . import cluster, ops
+
+IVFResult = namedtuple("IVFResult", ["ids", "scores", "probes", "scanned"])
+IVFResult.__doc__ = """ids int64 [nq, k] and scores fp32 [nq, k]: the first k candidates of every query, best first (-1 / NaN beyond
+its candidates); probes int64 [nq, nprobe]: the lists it probed, best first; scanned int64 [nq]: its candidates."""
+
+CANDIDATE_MEMORY_CAP = 4 << 30    # bytes of candidate scores and ids ([chunk, capacity] fp32 + int64) one step of search may hold
+
+
+def item_bound(tiles_np, tiles_all, nq):
+    """An upper bound on the work items of ``ops.ivf_scan`` for ``nq`` queries that probe distinct lists each: list l makes
+    ``tiles(l) * ceil(e(l) / G)`` items for its ``e(l)`` probing queries, and ``ceil(e / G) <= (e + G - 1) / G``, so the items are at
+    most ``(sum_l tiles(l) e(l) + (G - 1) * sum_{l probed} tiles(l)) / G``.  The first sum is at most ``nq * tiles_np`` (``tiles_np``:
+    the tiles of the ``nprobe`` lists with the most tiles), the second at most ``min(tiles_all, nq * tiles_np)``."""
+    g = ops.IVF_QUERY_GROUP
+    shared = nq * tiles_np
+    return max(1, (shared + (g - 1) * min(tiles_all, shared)) // g)
+
+
+class IVFIndex:
+    """The inverted file of ``rows`` over ``centroids`` -- the module docstring states the contract."""
+
+    def __init__(self, rows, centroids, labels=None, chunk=None):
+        _rows_matrix(rows, "rows")
+        cluster._matrix(centroids, "centroids")
+        if centroids.shape[1] != rows.shape[1]:
+            raise ValueError("centroids are [K, %d] and rows [N, %d]: the dimensions differ" % (centroids.shape[1], rows.shape[1]))
+        n, k = rows.shape[0], centroids.shape[0]
+        if labels is not None:
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+                raise ValueError("labels must be an int64 [%d] tensor, got %s" % (
+                    n, "%s %s" % (labels.dtype, tuple(labels.shape)) if isinstance(labels, torch.Tensor) else type(labels).__name__))
+        elif not rows.is_contiguous():
+            raise ValueError("rows must be contiguous to be assigned (labels=None)")
+        if chunk is not None:
+            cluster._count(chunk, "chunk")
+        cluster._on_device(rows, "rows")
+        cluster._on_device(centroids, "centroids")
+        if centroids.device != rows.device:
+            raise ValueError("centroids are on %s and rows on %s" % (centroids.device, rows.device))
+        if labels is not None:
+            cluster._on_device(labels, "labels")
+            if labels.device != rows.device:
+                raise ValueError("labels are on %s and rows on %s" % (labels.device, rows.device))
+            low, high = int(labels.min()), int(labels.max())
+            if low < 0 or high >= k:
+                raise ValueError("labels must lie in [0, %d), got %d .. %d" % (k, low, high))
+        else:
+            labels = cluster.assign(centroids, rows, chunk)[0]
+        self.rows, self.centroids, self.labels, self.fit = rows, centroids, labels, None
+        self.n, self.d, self.lists = n, rows.shape[1], k
+        self.order, self.offsets, self.sizes = cluster._members(labels, k)
+        # the one read-back: list sizes, and what follows from them for every nprobe
+        self.host_sizes = self.sizes.cpu().tolist()
+        by_size = sorted(self.host_sizes, reverse=True)
+        self._capacity, self._tiles = [0], [0]
+        for s in by_size:
+            self._capacity.append(self._capacity[-1] + s)
+            self._tiles.append(self._tiles[-1] + -(-s // ops.IVF_TILE))
+        self.coarse = ops.DescriptorIndex(centroids, "ND")
+
+    @classmethod
+    def train(cls, rows, lists, **kmeans_kwargs):
+        """The index of ``cluster.kmeans(rows, lists, **kmeans_kwargs)``; the fit stays reachable as ``.fit``."""
+        fit = cluster.kmeans(rows, lists, **kmeans_kwargs)
+        index = cls(rows, fit.centroids, fit.labels)
+        index.fit = fit
+        return index
+
+    def capacity(self, nprobe):
+        """The most candidates a query can have with ``nprobe`` probes: the sum of the ``nprobe`` largest list sizes (at least 1)."""
+        return max(1, self._capacity[nprobe])
+
+    def items(self, nq, nprobe):
+        """The workgroups ``search`` launches for the scan of ``nq`` queries: :func:`item_bound` of this index."""
+        return item_bound(self._tiles[nprobe], self._tiles[-1], nq)
+
+    def query_chunk(self, nprobe):
+        """Queries per step of ``search``: as many as keep the candidate block under ``CANDIDATE_MEMORY_CAP`` bytes (at least one)."""
+        return max(1, CANDIDATE_MEMORY_CAP // (12 * self.capacity(nprobe)))
+
+    def _check_search(self, queries, k, nprobe, qlayout, center):
+        if self.coarse is None:
+            raise ValueError("the index is closed")
+        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32 or queries.dim() != 2 or queries.numel() < 1:
+            raise ValueError("queries must be a non-empty fp32 2-d tensor, got %s" % (
+                "%s %s" % (queries.dtype, tuple(queries.shape)) if isinstance(queries, torch.Tensor) else type(queries).__name__))
+        if qlayout not in ("ND", "DN"):
+            raise ValueError("qlayout %r (\"ND\" or \"DN\")" % (qlayout,))
+        dq = queries.shape[1] if qlayout == "ND" else queries.shape[0]
+        if dq != self.d:
+            raise ValueError("queries have dimension %d and the rows %d" % (dq, self.d))
+        if not queries.is_contiguous():
+            raise ValueError("queries must be contiguous")
+        cluster._count(k, "k")
+        if k > ops.RESCORE_MAX_K:
+            raise ValueError("k = %d > %d" % (k, ops.RESCORE_MAX_K))
+        cluster._count(nprobe, "nprobe")
+        if nprobe > self.lists:
+            raise ValueError("nprobe = %d > %d lists" % (nprobe, self.lists))
+        if center is not None and (not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.numel() != self.d
+                                   or not center.is_contiguous()):
+            raise ValueError("center must be a contiguous fp32 tensor of %d elements" % self.d)
+        cluster._on_device(queries, "queries")
+        if queries.device != self.rows.device:
+            raise ValueError("queries are on %s and rows on %s" % (queries.device, self.rows.device))
+        if center is not None and center.device != self.rows.device:
+            raise ValueError("center is on %s and rows on %s" % (center.device, self.rows.device))
+
+    def search(self, queries, k, nprobe, qlayout="ND", center=None):
+        """:data:`IVFResult` of the ``k`` best rows of every query among the members of its ``nprobe`` best lists -- the module
+        docstring has the contract."""
+        self._check_search(queries, k, nprobe, qlayout, center)
+        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
+        chunk = self.query_chunk(nprobe)
+        if nq <= chunk:
+            return self._search(queries, k, nprobe, qlayout, center)
+        parts = []
+        for q0 in range(0, nq, chunk):
+            block = queries[q0:q0 + chunk] if qlayout == "ND" else queries[:, q0:q0 + chunk].contiguous()
+            parts.append(self._search(block, k, nprobe, qlayout, center))
+        return IVFResult(*(torch.cat([p[i] for p in parts]) for i in range(4)))
+
+    def _search(self, queries, k, nprobe, qlayout, center):
+        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
+        probes, _ = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
+        cap = self.capacity(nprobe)
+        plan = ops.ivf_plan(probes, self.offsets, self.n, cap)
+        cand_scores, cand_ids = ops.ivf_scan(self.rows, self.order, self.offsets, queries, plan, nprobe, cap, self.items(nq, nprobe),
+                                             qlayout, None if center is None else center.reshape(-1))
+        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k)
+        scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
+        return IVFResult(ids, scores, probes, scanned)
+
+    def close(self):
+        """Releases the coarse index."""
+        if self.coarse is not None:
+            self.coarse.close()
+            self.coarse = None
+
+
+def _rows_matrix(t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("%s must be a non-empty fp32 [rows, D] tensor, got %s" % (
+            what, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError("%s must have contiguous rows" % what)

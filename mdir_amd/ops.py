@@ -1711,6 +1711,134 @@ def kmeans_finish(sums, eps=1e-6, previous=None):
     return out
 
 
+# ------------------------------------------------------------------ inverted file (include/mdx_ivf.h)
+
+IVF_QUERY_GROUP = 8               # include/mdx_ivf.h MDX_IVF_QUERY_GROUP: entries (query, probe) that share a tile in one workgroup
+IVF_TILE = 64                     # include/mdx_ivf.h MDX_IVF_TILE: members of a list per workgroup of the scan
+
+
+def _ivf_count(x, who, what, lo=1):
+    if isinstance(x, bool) or not isinstance(x, int) or x < lo:
+        raise ValueError("%s: %s must be an integer >= %d, got %r" % (who, what, lo, x))
+
+
+def _ivf_vector(t, dtype, who, what, shape, device):
+    """``t`` is a contiguous device tensor of ``dtype`` and ``shape`` on ``device``, or a ValueError names it."""
+    _kmeans_tensor(t, dtype, who, what, len(shape))
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != device:
+        raise ValueError("%s: %s must be a contiguous %s tensor on %s, got %s on %s" % (who, what, list(shape), device, tuple(t.shape), t.device))
+    return _vp(t.data_ptr())
+
+
+def _ivf_plan_arg(plan, who, nq, nprobe, k, device):
+    _kmeans_tensor(plan, torch.uint8, who, "plan", 1)
+    need = _lib.lib().mdx_ivf_plan_workspace(nq, nprobe, k)
+    if need == 0:
+        raise ValueError("%s: nq = %d, nprobe = %d, K = %d: nprobe must be in [1, K] and nq * nprobe below 2^31" % (who, nq, nprobe, k))
+    if not plan.is_contiguous() or plan.device != device:
+        raise ValueError("%s: plan must be a contiguous uint8 tensor on %s" % (who, device))
+    return _vp(plan.data_ptr())
+
+
+def ivf_plan_views(plan, nq, nprobe, k):
+    """The sections of a plan (include/mdx_ivf.h) as int64 views of it: ``{"base": [nq, nprobe], "count": [nq], "first": [k + 1],
+    "item": [k + 1], "entry": [nq * nprobe]}``.  Of ``entry`` only the first ``first[k]`` are defined, and inside a list in no
+    particular order."""
+    up = lambda b: (b + 255) // 256 * 256
+    words = plan[:plan.numel() // 8 * 8].view(torch.int64)
+    views, at = {}, 0
+    for name, shape in (("base", (nq, nprobe)), ("count", (nq,)), ("first", (k + 1,)), ("item", (k + 1,)), ("entry", (nq * nprobe,))):
+        count = int(np.prod(shape))
+        views[name] = words[at // 8:at // 8 + count].view(shape)
+        at += up(8 * count)
+    return views
+
+
+def ivf_plan(probes, offsets, m, cap):
+    """The plan (a uint8 device tensor of ``mdx_ivf_plan_workspace`` bytes; :func:`ivf_plan_views` names its sections) of a batch
+    of probes (``mdx_ivf_plan``).  ``probes`` int64 ``[nq, nprobe]``: the lists every query probes, best first (a probe outside
+    ``[0, K)`` is skipped); ``offsets`` int64 ``[K + 1]``: list l owns ``members[offsets[l]:offsets[l + 1]]`` of ``m`` members;
+    ``cap``: the columns of a query's candidate row."""
+    who = "ivf_plan"
+    _kmeans_tensor(probes, torch.int64, who, "probes", 2)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    nq, nprobe = probes.shape
+    k = offsets.shape[0] - 1
+    _ivf_vector(probes, torch.int64, who, "probes", (nq, nprobe), probes.device)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), probes.device)
+    _ivf_count(m, who, "m")
+    _ivf_count(cap, who, "cap")
+    if k < 1 or nprobe > k:
+        raise ValueError("%s: nprobe = %d probes of K = %d lists: nprobe must be in [1, K]" % (who, nprobe, k))
+    h = _lib.lib()
+    plan = _workspace(h.mdx_ivf_plan_workspace(nq, nprobe, k), probes.device)
+    with _on(probes):
+        check(h.mdx_ivf_plan(_vp(probes.data_ptr()), nq, nprobe, _vp(offsets.data_ptr()), k, m, cap, _vp(plan.data_ptr()), plan.numel(),
+                             _stream()), "mdx_ivf_plan")
+    return plan
+
+
+def ivf_scan(rows, members, offsets, queries, plan, nprobe, cap, items, qlayout="ND", center=None):
+    """``(cand_scores fp32 [nq, cap], cand_ids int64 [nq, cap])``: the exact fp32 chain scores of every query against the members of
+    the lists it probes (``mdx_ivf_scan``), list-major: a tile of a list is read once for up to ``IVF_QUERY_GROUP`` queries that probe
+    it.  ``rows`` fp32 ``[n, d]`` on the device (rows contiguous at any stride); ``members`` int64 ``[m]`` and ``offsets`` int64
+    ``[K + 1]``: the lists; ``plan``: :func:`ivf_plan` of the probes with the same ``offsets``, ``m = members.numel()`` and ``cap``;
+    ``items``: the workgroups to launch, at least the plan's number of work items (``ivf.item_bound``).  A candidate's column is the
+    base of its probe plus its index in the list; columns at or beyond a query's count hold NaN / -1; a member id outside ``[0, n)``
+    scores NaN.  Every score is bit-identical to ``DescriptorIndex(rows, "ND").scores(queries, qlayout, center)`` at the same id."""
+    who = "ivf_scan"
+    rp, ld = _kmeans_matrix(rows, who, "rows")
+    n, d = rows.shape
+    _kmeans_tensor(queries, torch.float32, who, "queries", 2)
+    nq, dq, lay = _layout(queries, qlayout, "queries")
+    if dq != d:
+        raise ValueError("%s: query dimension %d != rows dimension %d" % (who, dq, d))
+    if not queries.is_contiguous() or queries.device != rows.device:
+        raise ValueError("%s: queries must be contiguous on %s" % (who, rows.device))
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    m, k = members.shape[0], offsets.shape[0] - 1
+    _ivf_vector(members, torch.int64, who, "members", (m,), rows.device)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), rows.device)
+    for x, what in ((nprobe, "nprobe"), (cap, "cap"), (items, "items")):
+        _ivf_count(x, who, what)
+    cp = None
+    if center is not None:
+        cp = _ivf_vector(center, torch.float32, who, "center", (d,), rows.device)
+    pp = _ivf_plan_arg(plan, who, nq, nprobe, k, rows.device)
+    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=rows.device)
+    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=rows.device)
+    with _on(rows):
+        check(_lib.lib().mdx_ivf_scan(rp, n, d, ld, _vp(members.data_ptr()), m, _vp(offsets.data_ptr()), k, _vp(queries.data_ptr()), nq, lay,
+                                      cp, nprobe, pp, plan.numel(), cap, items, _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()),
+                                      _stream()), "mdx_ivf_scan")
+    return cand_scores, cand_ids
+
+
+def ivf_select(cand_scores, cand_ids, plan, nprobe, lists, k):
+    """``(ids int64 [nq, k], scores fp32 [nq, k])``: per query the first ``k`` of its candidates (the plan's count of them, the
+    leading columns of ``cand_scores`` / ``cand_ids``, both ``[nq, cap]``) in :func:`rank_full`'s order -- larger score first,
+    ``-0 == +0``, NaN last, equal keys by ascending id -- sorted (``mdx_ivf_select``); positions beyond the count hold -1 / NaN.
+    ``lists``: the K of the plan."""
+    who = "ivf_select"
+    _kmeans_tensor(cand_scores, torch.float32, who, "cand_scores", 2)
+    nq, cap = cand_scores.shape
+    _ivf_vector(cand_scores, torch.float32, who, "cand_scores", (nq, cap), cand_scores.device)
+    _kmeans_tensor(cand_ids, torch.int64, who, "cand_ids", 2)
+    _ivf_vector(cand_ids, torch.int64, who, "cand_ids", (nq, cap), cand_scores.device)
+    for x, what in ((nprobe, "nprobe"), (lists, "lists")):
+        _ivf_count(x, who, what)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= RESCORE_MAX_K:
+        raise ValueError("%s: k must be an integer in [1, %d], got %r" % (who, RESCORE_MAX_K, k))
+    pp = _ivf_plan_arg(plan, who, nq, nprobe, lists, cand_scores.device)
+    out_ids = torch.empty((nq, k), dtype=torch.int64, device=cand_scores.device)
+    out_scores = torch.empty((nq, k), dtype=torch.float32, device=cand_scores.device)
+    with _on(cand_scores):
+        check(_lib.lib().mdx_ivf_select(_vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()), nq, cap, nprobe, lists, pp, plan.numel(), k,
+                                        _vp(out_ids.data_ptr()), _vp(out_scores.data_ptr()), _stream()), "mdx_ivf_select")
+    return out_ids, out_scores
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
