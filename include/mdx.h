@@ -994,6 +994,17 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * launching ones have cases in tests/test_gpu_ivf_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_ivf.h"
 
+/* --------------------------------------------------- inverted file, int8 lists */
+
+/* The rows of the lists a second time as MDX_I8 codes in list order, and a first stage of the search that scans them on the int8 MFMA:
+ * a quarter of the bytes, read as a contiguous stream where the fp32 scan gathers whole rows.  The plan, the work items and the
+ * selection are those of mdx_ivf.h; the candidates are then rescored exactly (mdx_rescore) and certified (mdx_rescore_certify).  The
+ * whole contract -- the storage, the scores to the bit, what the certified prefix of a result equals and why, the refusals -- is
+ * stated in mdx_lists_i8.h, beside this file, with the prototypes; their names are in _lib.LISTS_I8_EXPORTS, for the reason given
+ * above for mdx_knn_join.h, and their census is tests/test_lists_i8_host.py (every prototype is exported and bound; the three have
+ * cases in tests/test_gpu_lists_i8_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_lists_i8.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

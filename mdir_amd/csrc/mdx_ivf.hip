@@ -7,60 +7,23 @@
 //             once per stage and serve the whole group, wave w runs the chains of entries w and w + 4.
 //   select    one workgroup per query: everything into LDS up to 4096 candidates, a radix select over (order key, id) above that,
 //             then a bitonic sort of the chosen pairs.
+//
+// The sections of the plan, the clamping of the offsets, the checks of the shared sizes and the pad launch of the scan are in
+// mdx_ivf_plan.h, which the int8 scan of the same work items (mdx_lists_i8.hip) includes too.
 #include "mdx_exact.h"
+#include "mdx_ivf_plan.h"
 
 namespace mdx {
 namespace {
 
-constexpr int G = MDX_IVF_QUERY_GROUP;
-constexpr int TC = MDX_IVF_TILE;            // members per tile: one per lane
-constexpr int KC = 256;                     // k per stage: one 1-KiB piece of every row
+constexpr int KC = 256;                   // k per stage: one 1-KiB piece of every row
 constexpr int LD = KC + 4;                  // floats per LDS row: lane r reads row r with ds_read_b128, banks 4r .. 4r+3 (mod 64)
 constexpr int ROWS_PER_WAVE = TC / 4;
 constexpr int QPW = G / 4;                  // entries per wave
 constexpr int SEL_THREADS = 1024;
 constexpr int SEL_MAX = MDX_RESCORE_MAX_K;
-constexpr int64_t LIMIT = 1ll << 31;
 
 static_assert(TC == 64 && G % 4 == 0 && G <= 64, "one member per lane, the entries dealt to four waves");
-
-// the sections of the plan (include/mdx_ivf.h)
-struct Plan {
-    int64_t *base, *count, *first, *item, *entry;
-    unsigned long long *cursor;
-};
-
-static inline int64_t plan_bytes_of(int64_t nq, int64_t nprobe, int64_t K)
-{
-    return 2 * round_up(8 * nq * nprobe, 256) + round_up(8 * nq, 256) + 2 * round_up(8 * (K + 1), 256) + round_up(16 * K, 256);
-}
-
-static inline Plan carve(const void *plan, int64_t nq, int64_t nprobe, int64_t K)
-{
-    char *p = (char *)plan;
-    Plan v;
-    v.base = (int64_t *)p;
-    p += round_up(8 * nq * nprobe, 256);
-    v.count = (int64_t *)p;
-    p += round_up(8 * nq, 256);
-    v.first = (int64_t *)p;
-    p += round_up(8 * (K + 1), 256);
-    v.item = (int64_t *)p;
-    p += round_up(8 * (K + 1), 256);
-    v.entry = (int64_t *)p;
-    p += round_up(8 * nq * nprobe, 256);
-    v.cursor = (unsigned long long *)p;
-    return v;
-}
-
-__device__ __forceinline__ int64_t clamp_to(int64_t o, int64_t hi) { return o < 0 ? 0 : o > hi ? hi : o; }
-
-// the members list l has after clamping its offsets to [0, m]
-__device__ __forceinline__ int64_t list_size(const int64_t *__restrict__ offsets, int64_t l, int64_t m)
-{
-    const int64_t lo = clamp_to(offsets[l], m), hi = clamp_to(offsets[l + 1], m);
-    return hi > lo ? hi - lo : 0;
-}
 
 // ------------------------------------------------------------------------------------------------------------------ plan
 
@@ -267,19 +230,6 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float *__restrict__
     }
 }
 
-// the columns at or beyond a query's count: NaN / -1.  One workgroup per (query, 1024 columns)
-__global__ __launch_bounds__(256) void ivf_pad_kernel(const int64_t *__restrict__ count, int64_t cap, int64_t blocks,
-                                                      float *__restrict__ cand_scores, int64_t *__restrict__ cand_ids)
-{
-    const int64_t q = (int64_t)blockIdx.x / blocks, c0 = ((int64_t)blockIdx.x % blocks) * 1024;
-    const int64_t have = clamp_to(count[q], cap);
-    const int64_t c1 = c0 + 1024 < cap ? c0 + 1024 : cap;
-    for (int64_t c = (c0 > have ? c0 : have) + threadIdx.x; c < c1; c += 256) {
-        cand_scores[q * cap + c] = __builtin_nanf("");
-        cand_ids[q * cap + c] = -1;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ select
 
 __device__ __forceinline__ uint64_t id_key(int64_t id) { return (uint64_t)id ^ (1ull << 63); }     // ascending as signed ids
@@ -424,25 +374,6 @@ __global__ __launch_bounds__(SEL_THREADS) void ivf_select_kernel(const float *__
         out_ids[q * k + i] = i < total ? sid[i] : -1;
         out_scores[q * k + i] = i < total ? ssc[i] : __builtin_nanf("");
     }
-}
-
-// the sizes every call shares, and the plan
-static int check_plan(const char *who, int64_t nq, int64_t nprobe, int64_t K, const void *plan, int64_t plan_bytes)
-{
-    MDX_CHECK_ARG(nq >= 1 && nprobe >= 1 && K >= 1, "%s: nq=%lld nprobe=%lld K=%lld must be >= 1", who, (long long)nq, (long long)nprobe,
-                  (long long)K);
-    MDX_CHECK_ARG(nq < LIMIT && K < LIMIT && nprobe <= K && nq * nprobe < LIMIT,
-                  "%s: nq=%lld nprobe=%lld K=%lld too large (nprobe > K, or a size or nq nprobe of 2^31 or more)", who, (long long)nq,
-                  (long long)nprobe, (long long)K);
-    MDX_CHECK_WORKSPACE(who, plan, plan_bytes, plan_bytes_of(nq, nprobe, K));
-    return MDX_OK;
-}
-
-static int check_cap(const char *who, int64_t nq, int64_t cap)
-{
-    MDX_CHECK_ARG(cap >= 1 && cap < LIMIT, "%s: cap=%lld must be in [1, 2^31)", who, (long long)cap);
-    MDX_CHECK_ARG(nq * ceil_div(cap, 1024) < LIMIT, "%s: nq=%lld cap=%lld too large for one launch", who, (long long)nq, (long long)cap);
-    return MDX_OK;
 }
 
 }  // namespace

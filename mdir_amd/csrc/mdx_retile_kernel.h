@@ -1,5 +1,6 @@
 // The re-tiling and int8 quantisation kernels of mdx_index.hip (the index build, the queries of every call, mdx_quantize_i8).
 #pragma once
+#include "mdx_i8_quant.h"
 #include "mdx_scores_i8_kernel.h"
 
 namespace mdx {
@@ -116,16 +117,7 @@ __global__ __launch_bounds__(256) void retile_block_kernel(const float *__restri
 // and i8_scale_kernel (a -> a / 127 in place).  mdx_quantize_i8 is the same three steps with row-major codes out.
 //   int8 tile = 16 rows x 64 k: lane (g, j), byte e = (row j, k 64 kb + 16 g + e)
 // ---------------------------------------------------------------------------
-constexpr int64_t I8_MAX_DPAD = 133120;        // largest multiple of 64 with 127^2 * d_pad < 2^31 (exact int32 accumulation)
-
-__device__ __forceinline__ float i8_inv(float a) { return __fdiv_rn(127.0f, a); }
-__device__ __forceinline__ float i8_scale(float a) { return __fdiv_rn(a, 127.0f); }
-__device__ __forceinline__ uint32_t i8_code(float x, float a, float inv)      // the code's byte
-{
-    if (a == 0.f) return 0u;
-    const float y = fminf(fmaxf(rintf(__fmul_rn(x, inv)), -127.f), 127.f);
-    return (uint32_t)(uint8_t)(int8_t)(int)y;
-}
+// I8_MAX_DPAD, i8_inv, i8_scale and i8_code: mdx_i8_quant.h, shared with mdx_lists_i8.hip
 // element (row, k) of the source, center[k] subtracted
 template <bool ROWMAJOR>
 __device__ __forceinline__ float i8_src(const float *src, int64_t n, int64_t d, const float *center, int64_t row, int64_t k)

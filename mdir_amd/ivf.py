@@ -5,7 +5,7 @@ The partition is ``cluster.kmeans``'s (or any labels), the rows stay where they 
 result is defined to the bit: with ``nprobe == lists`` it is ``ops.topk(index.scores(q), k)`` of an fp32 ``DescriptorIndex`` of the
 rows, with fewer probes it is that ranking restricted to the rows of the probed lists.  ``tests/ivf_restatement.py`` states it in numpy.
 
-``IVFIndex(rows, centroids, labels=None, chunk=None)``
+``IVFIndex(rows, centroids, labels=None, chunk=None, storage="f32")``
     ``rows`` fp32 ``[N, D]`` on the device, rows contiguous at any row stride (as ``ops.rescore`` accepts); read in place, never
     copied or permuted.  ``centroids`` fp32 ``[K, D]`` on the same device, contiguous.  ``labels`` int64 ``[N]`` in ``[0, K)``: the
     list of every row; ``None`` means ``cluster.assign(centroids, rows, chunk)[0]`` (``rows`` must then be contiguous).  Explicit
@@ -17,7 +17,11 @@ rows, with fewer probes it is that ranking restricted to the rows of the probed 
     capacity of a query (``capacity(nprobe)``: the sum of the ``nprobe`` largest lists) and a bound on the scan's work items
     (:func:`item_bound`), so a search reads nothing back.
 
-``IVFIndex.train(rows, lists, **kmeans_kwargs)``
+    ``storage="i8"`` (``include/mdx_lists_i8.h``) also keeps ``codes`` (int8 ``[N, round_up(D, 64)]``) and ``scales`` (fp32 ``[N]``),
+    the ``MDX_I8`` quantisation of the rows in list order (``ops.lists_i8_encode`` of ``order``), and ``bounds``
+    (``ops.lists_i8_bounds``), all built once here.  The fp32 rows stay: the exact second stage reads them.  ``D <= 133120``.
+
+``IVFIndex.train(rows, lists, storage="f32", **kmeans_kwargs)``
     ``cluster.kmeans(rows, lists, **kmeans_kwargs)``, then the index of ``fit.centroids`` and ``fit.labels``; the :data:`KMeans`
     result stays reachable as ``.fit``.
 
@@ -34,6 +38,23 @@ rows, with fewer probes it is that ranking restricted to the rows of the probed 
     candidate block stays under ``CANDIDATE_MEMORY_CAP`` bytes; the chunk changes no bit of the result.  Nothing is read back and
     nothing synchronises.  There is no CPU fallback.
 
+``index.search(queries, k, nprobe, qlayout="ND", center=None, shortlist=None, exact=False)`` on an ``"i8"`` index -> :data:`IVFRescored`
+    Steps 1 and 2 as above.  3. ``ops.lists_i8_scan`` on ``ops.quantize_i8(ops.center_rows(queries, qlayout, center))``: the same work
+    items on the int8 MFMA, over the contiguous codes; the candidate scores are the bits of
+    ``ops.DescriptorIndex(rows, "ND", storage="i8").scores(queries, qlayout, center)`` at the same id.
+    ``shortlist=None``: the int8 ranking -- ``ops.ivf_select`` of those candidates; ``certified`` is ``None`` and ``fallback`` empty.
+    ``shortlist=S`` (``k <= S <= ops.RESCORE_MAX_K``): ``ops.ivf_select`` takes ``S`` candidates by int8 score, ``ops.rescore``
+    scores them with the exact chain on ``rows`` and sorts them, ``ops.rescore_certify`` (``t`` = the S-th int8 score, ``bounds``)
+    gives the depth, and the first ``k`` are returned.  The first ``certified[q]`` entries are, bit for bit, the first entries of
+    ``IVFIndex(rows, centroids, labels).search(queries, k, nprobe, qlayout, center)`` -- the proof is in ``include/mdx_lists_i8.h``.
+    Where ``scanned[q] <= S`` every candidate was rescored: ``certified[q] = S`` and the whole row, padding included, is the fp32
+    index's.  (The -1 ids that pad a shortlist go to ``ops.rescore`` as the id ``N``, which it never dereferences either, so that they
+    sort behind a candidate whose chain score is NaN, where the fp32 search has its padding; they come back as -1.)
+    ``exact=True`` (needs ``shortlist``): the queries with ``certified < k`` are run again through the fp32 scan of this index
+    (``ops.ivf_scan`` on ``rows``) and ``fallback`` (int64, ascending) lists them; the whole result then equals the fp32 index's.  This
+    is the one read-back of a search: ``nonzero`` of ``certified < k``.  ``shortlist`` and ``exact`` are a ``ValueError`` on an
+    ``"f32"`` index.  ``query_chunk(nprobe, shortlist)`` counts the query codes and the shortlist's buffers as well.
+
 ``index.close()`` releases the coarse index.
 """
 from collections import namedtuple
@@ -45,6 +66,12 @@ from . import cluster, ops
 IVFResult = namedtuple("IVFResult", ["ids", "scores", "probes", "scanned"])
 IVFResult.__doc__ = """ids int64 [nq, k] and scores fp32 [nq, k]: the first k candidates of every query, best first (-1 / NaN beyond
 its candidates); probes int64 [nq, nprobe]: the lists it probed, best first; scanned int64 [nq]: its candidates."""
+
+IVFRescored = namedtuple("IVFRescored", ["ids", "scores", "probes", "scanned", "certified", "fallback"])
+IVFRescored.__doc__ = """ids, scores, probes, scanned as in :data:`IVFResult`; certified int64 [nq]: the leading entries that are, bit for
+bit, the fp32 index's (None without a shortlist); fallback int64 [f]: the queries answered by the fp32 scan (empty unless exact=True)."""
+
+STORAGES = ("f32", "i8")
 
 CANDIDATE_MEMORY_CAP = 4 << 30    # bytes of candidate scores and ids ([chunk, capacity] fp32 + int64) one step of search may hold
 
@@ -62,7 +89,11 @@ def item_bound(tiles_np, tiles_all, nq):
 class IVFIndex:
     """The inverted file of ``rows`` over ``centroids`` -- the module docstring states the contract."""
 
-    def __init__(self, rows, centroids, labels=None, chunk=None):
+    storage, codes, scales, bounds = "f32", None, None, None
+
+    def __init__(self, rows, centroids, labels=None, chunk=None, storage="f32"):
+        if storage not in STORAGES:
+            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
         _rows_matrix(rows, "rows")
         cluster._matrix(centroids, "centroids")
         if centroids.shape[1] != rows.shape[1]:
@@ -99,13 +130,19 @@ class IVFIndex:
         for s in by_size:
             self._capacity.append(self._capacity[-1] + s)
             self._tiles.append(self._tiles[-1] + -(-s // ops.IVF_TILE))
+        self.storage = storage
+        if storage == "i8":
+            self.codes, self.scales = ops.lists_i8_encode(rows, self.order)
+            self.bounds = ops.lists_i8_bounds(self.codes, self.scales, self.d)
         self.coarse = ops.DescriptorIndex(centroids, "ND")
 
     @classmethod
-    def train(cls, rows, lists, **kmeans_kwargs):
+    def train(cls, rows, lists, storage="f32", **kmeans_kwargs):
         """The index of ``cluster.kmeans(rows, lists, **kmeans_kwargs)``; the fit stays reachable as ``.fit``."""
+        if storage not in STORAGES:
+            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
         fit = cluster.kmeans(rows, lists, **kmeans_kwargs)
-        index = cls(rows, fit.centroids, fit.labels)
+        index = cls(rows, fit.centroids, fit.labels, storage=storage)
         index.fit = fit
         return index
 
@@ -117,9 +154,14 @@ class IVFIndex:
         """The workgroups ``search`` launches for the scan of ``nq`` queries: :func:`item_bound` of this index."""
         return item_bound(self._tiles[nprobe], self._tiles[-1], nq)
 
-    def query_chunk(self, nprobe):
-        """Queries per step of ``search``: as many as keep the candidate block under ``CANDIDATE_MEMORY_CAP`` bytes (at least one)."""
-        return max(1, CANDIDATE_MEMORY_CAP // (12 * self.capacity(nprobe)))
+    def query_chunk(self, nprobe, shortlist=None):
+        """Queries per step of ``search``: as many as keep the candidate block under ``CANDIDATE_MEMORY_CAP`` bytes (at least one).  On an
+        int8 index a query also holds its centred row, codes and scale (``5 d + 4`` bytes) and, with a shortlist of ``S``, the int8
+        selection, the rescored pairs and the unsorted scores (``28 S``) and its depth and bound (8)."""
+        per_query = 12 * self.capacity(nprobe)
+        if self.storage == "i8":
+            per_query += 5 * self.d + 4 + (0 if shortlist is None else 28 * shortlist + 8)
+        return max(1, CANDIDATE_MEMORY_CAP // per_query)
 
     def _check_search(self, queries, k, nprobe, qlayout, center):
         if self.coarse is None:
@@ -149,21 +191,51 @@ class IVFIndex:
         if center is not None and center.device != self.rows.device:
             raise ValueError("center is on %s and rows on %s" % (center.device, self.rows.device))
 
-    def search(self, queries, k, nprobe, qlayout="ND", center=None):
-        """:data:`IVFResult` of the ``k`` best rows of every query among the members of its ``nprobe`` best lists -- the module
-        docstring has the contract."""
+    def _check_stages(self, k, shortlist, exact):
+        cluster._count(k, "k")
+        if not isinstance(exact, bool):
+            raise ValueError("exact must be a bool, got %r" % (exact,))
+        if self.storage != "i8":
+            if shortlist is not None or exact:
+                raise ValueError("shortlist and exact need an int8 index (storage=\"i8\"); this one is %s" % self.storage)
+            return
+        if shortlist is not None:
+            cluster._count(shortlist, "shortlist")
+            if not k <= shortlist <= ops.RESCORE_MAX_K:
+                raise ValueError("shortlist = %d must be in [k = %d, %d]" % (shortlist, k, ops.RESCORE_MAX_K))
+        elif exact:
+            raise ValueError("exact=True needs a shortlist")
+
+    def search(self, queries, k, nprobe, qlayout="ND", center=None, shortlist=None, exact=False):
+        """:data:`IVFResult` (an int8 index: :data:`IVFRescored`) of the ``k`` best rows of every query among the members of its
+        ``nprobe`` best lists -- the module docstring has the contract."""
+        self._check_stages(k, shortlist, exact)
         self._check_search(queries, k, nprobe, qlayout, center)
+        if self.storage != "i8":
+            return self._chunked(self._search, IVFResult, self.query_chunk(nprobe), queries, qlayout, k, nprobe, center)
+        res = self._chunked(self._search_i8, IVFRescored, self.query_chunk(nprobe, shortlist), queries, qlayout, k, nprobe, center, shortlist)
+        if not exact:
+            return res
+        fallback = torch.nonzero(res.certified < k).reshape(-1)                 # the one read-back: how many queries run again
+        if fallback.numel():
+            again = queries[fallback] if qlayout == "ND" else queries[:, fallback].contiguous()
+            sure = self._chunked(self._search, IVFResult, self.query_chunk(nprobe), again, qlayout, k, nprobe, center)
+            res.ids.index_copy_(0, fallback, sure.ids)
+            res.scores.index_copy_(0, fallback, sure.scores)
+        return res._replace(fallback=fallback)
+
+    def _chunked(self, step, kind, chunk, queries, qlayout, *args):
+        """``step`` on the queries ``chunk`` at a time; the parts of every field back to back (a field that is None stays None)."""
         nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
-        chunk = self.query_chunk(nprobe)
         if nq <= chunk:
-            return self._search(queries, k, nprobe, qlayout, center)
+            return step(queries, qlayout, *args)
         parts = []
         for q0 in range(0, nq, chunk):
             block = queries[q0:q0 + chunk] if qlayout == "ND" else queries[:, q0:q0 + chunk].contiguous()
-            parts.append(self._search(block, k, nprobe, qlayout, center))
-        return IVFResult(*(torch.cat([p[i] for p in parts]) for i in range(4)))
+            parts.append(step(block, qlayout, *args))
+        return kind(*(None if parts[0][i] is None else torch.cat([p[i] for p in parts]) for i in range(len(parts[0]))))
 
-    def _search(self, queries, k, nprobe, qlayout, center):
+    def _search(self, queries, qlayout, k, nprobe, center):
         nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
         probes, _ = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
         cap = self.capacity(nprobe)
@@ -173,6 +245,28 @@ class IVFIndex:
         ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k)
         scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
         return IVFResult(ids, scores, probes, scanned)
+
+    def _search_i8(self, queries, qlayout, k, nprobe, center, shortlist):
+        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
+        center = None if center is None else center.reshape(-1)
+        probes, _ = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
+        cap = self.capacity(nprobe)
+        plan = ops.ivf_plan(probes, self.offsets, self.n, cap)
+        qcodes, qscales = ops.quantize_i8(ops.center_rows(queries, qlayout, center))
+        cand_scores, cand_ids = ops.lists_i8_scan(self.codes, self.scales, self.d, self.order, self.offsets, qcodes, qscales, plan, nprobe,
+                                                  cap, self.items(nq, nprobe))
+        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k if shortlist is None else shortlist)
+        scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
+        none = torch.empty(0, dtype=torch.int64, device=self.rows.device)
+        if shortlist is None:
+            return IVFRescored(ids, scores, probes, scanned, None, none)
+        del cand_scores, cand_ids
+        # the padding of a shortlist as the id n: not dereferenced, NaN, and behind every candidate in the order of the rescored row
+        sure_ids, sure = ops.rescore(self.rows, queries, torch.where(ids < 0, self.n, ids), qlayout, center)
+        sure_ids = torch.where(sure_ids >= self.n, -1, sure_ids)
+        depth, _ = ops.rescore_certify(sure, scores[:, shortlist - 1], queries, self.bounds, max(self.n, shortlist), qlayout, center)
+        certified = torch.where(scanned <= shortlist, shortlist, depth.to(torch.int64))
+        return IVFRescored(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned, certified, none)
 
     def close(self):
         """Releases the coarse index."""

@@ -1839,6 +1839,90 @@ def ivf_select(cand_scores, cand_ids, plan, nprobe, lists, k):
     return out_ids, out_scores
 
 
+# ------------------------------------------------------------------ inverted file, int8 lists (include/mdx_lists_i8.h)
+
+LISTS_I8_MAX_D = 133120           # include/mdx.h MDX_I8: 127^2 * round_up(d, 64) stays below 2^31
+
+
+def _lists_i8_storage(codes, scales, d, who):
+    """``codes`` int8 ``[m, round_up(d, 64)]`` and ``scales`` fp32 ``[m]`` of :func:`lists_i8_encode`, checked; ``(pointers, m)``."""
+    _kmeans_tensor(codes, torch.int8, who, "codes", 2)
+    _ivf_count(d, who, "d")
+    if d > LISTS_I8_MAX_D:
+        raise ValueError("%s: d = %d > %d" % (who, d, LISTS_I8_MAX_D))
+    m, d_pad = codes.shape[0], (d + 63) // 64 * 64
+    _ivf_vector(codes, torch.int8, who, "codes", (m, d_pad), codes.device)
+    _kmeans_tensor(scales, torch.float32, who, "scales", 1)
+    _ivf_vector(scales, torch.float32, who, "scales", (m,), codes.device)
+    return _vp(codes.data_ptr()), _vp(scales.data_ptr()), m
+
+
+def lists_i8_encode(rows, members):
+    """``(codes int8 [m, round_up(d, 64)], scales fp32 [m])``: the ``MDX_I8`` quantisation of the rows of the lists, in list order
+    (``mdx_lists_i8_encode``).  Position ``p`` holds the bits ``quantize_i8`` gives for row ``members[p]`` and zeros in the padding
+    columns; a member id outside ``[0, n)`` is never dereferenced and gets zero codes and a NaN scale.  ``rows`` fp32 ``[n, d]`` on the
+    device (rows contiguous at any stride, read in place); ``members`` int64 ``[m]``."""
+    who = "lists_i8_encode"
+    rp, ld = _kmeans_matrix(rows, who, "rows")
+    n, d = rows.shape
+    if d > LISTS_I8_MAX_D:
+        raise ValueError("%s: d = %d > %d" % (who, d, LISTS_I8_MAX_D))
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    m = members.shape[0]
+    _ivf_vector(members, torch.int64, who, "members", (m,), rows.device)
+    codes = torch.empty((m, (d + 63) // 64 * 64), dtype=torch.int8, device=rows.device)
+    scales = torch.empty((m,), dtype=torch.float32, device=rows.device)
+    with _on(rows):
+        check(_lib.lib().mdx_lists_i8_encode(rp, n, d, ld, _vp(members.data_ptr()), m, _vp(codes.data_ptr()), _vp(scales.data_ptr()),
+                                             _stream()), "mdx_lists_i8_encode")
+    return codes, scales
+
+
+def lists_i8_bounds(codes, scales, d):
+    """Device tensor (float64 ``[4]``, the bytes of ``mdx_i8_bounds``, as :meth:`DescriptorIndex.i8_bounds` returns) of the storage of
+    :func:`lists_i8_encode` (``mdx_lists_i8_bounds``): for valid members the values of an int8 ``DescriptorIndex`` of the same rows,
+    to the bit; a non-finite scale sets the flag.  ``d``: the dimension of the rows.  What :func:`rescore_certify` needs."""
+    who = "lists_i8_bounds"
+    cp, sp, m = _lists_i8_storage(codes, scales, d, who)
+    b = torch.empty(4, dtype=torch.float64, device=codes.device)
+    with _on(codes):
+        check(_lib.lib().mdx_lists_i8_bounds(cp, sp, m, d, _vp(b.data_ptr()), _stream()), "mdx_lists_i8_bounds")
+    return b
+
+
+def lists_i8_scan(codes, scales, d, members, offsets, qcodes, qscales, plan, nprobe, cap, items):
+    """``(cand_scores fp32 [nq, cap], cand_ids int64 [nq, cap])``: the ``MDX_I8`` scores of every query against the members of the
+    lists it probes (``mdx_lists_i8_scan``), on the int8 MFMA over the contiguous codes of :func:`lists_i8_encode`.  ``members``,
+    ``offsets``, ``plan``, ``nprobe``, ``cap``, ``items`` and the outputs are those of :func:`ivf_scan`; ``qcodes`` int8 ``[nq, d]`` and
+    ``qscales`` fp32 ``[nq]`` are ``quantize_i8(center_rows(queries, qlayout, center))``.  Every score is bit-identical to
+    ``DescriptorIndex(rows, "ND", storage="i8").scores(queries, qlayout, center)`` at the same id; a member whose scale is NaN (an id
+    outside the rows) scores NaN."""
+    who = "lists_i8_scan"
+    cp, sp, m = _lists_i8_storage(codes, scales, d, who)
+    _kmeans_tensor(qcodes, torch.int8, who, "qcodes", 2)
+    nq, dq = qcodes.shape
+    if dq != d:
+        raise ValueError("%s: query dimension %d != rows dimension %d" % (who, dq, d))
+    _ivf_vector(qcodes, torch.int8, who, "qcodes", (nq, d), codes.device)
+    _kmeans_tensor(qscales, torch.float32, who, "qscales", 1)
+    _ivf_vector(qscales, torch.float32, who, "qscales", (nq,), codes.device)
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    k = offsets.shape[0] - 1
+    _ivf_vector(members, torch.int64, who, "members", (m,), codes.device)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), codes.device)
+    for x, what in ((nprobe, "nprobe"), (cap, "cap"), (items, "items")):
+        _ivf_count(x, who, what)
+    pp = _ivf_plan_arg(plan, who, nq, nprobe, k, codes.device)
+    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=codes.device)
+    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=codes.device)
+    with _on(codes):
+        check(_lib.lib().mdx_lists_i8_scan(cp, sp, m, d, _vp(members.data_ptr()), _vp(offsets.data_ptr()), k, _vp(qcodes.data_ptr()),
+                                           _vp(qscales.data_ptr()), nq, nprobe, pp, plan.numel(), cap, items,
+                                           _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()), _stream()), "mdx_lists_i8_scan")
+    return cand_scores, cand_ids
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
