@@ -1005,6 +1005,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * cases in tests/test_gpu_lists_i8_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_lists_i8.h"
 
+/* ------------------------------------- inverted file, product-quantised lists */
+
+/* The rows of the lists as M bytes each: the residual of a row against its list's centroid, cut into M sub-vectors, every one replaced
+ * by the id of its nearest of 256 codewords (IVF-PQ).  A search builds one look-up table per query -- the exact chain of its
+ * sub-vectors with every codeword -- and scans the codes by table look-ups (asymmetric distance computation); the fp32 rows are needed
+ * only for an optional exact second stage (mdx_rescore).  The plan and the selection are those of mdx_ivf.h.  The whole contract -- the
+ * table and the score to the bit, the layout of the codes, the launch shape, the refusals -- is stated in mdx_lists_pq.h, beside this
+ * file, with the prototypes and MDX_PQ_MAX_M; their names are in _lib.LISTS_PQ_EXPORTS, for the reason given above for mdx_knn_join.h,
+ * and their census is tests/test_pq_host.py (every prototype is exported and bound; both have cases in
+ * tests/test_gpu_lists_pq_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_lists_pq.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -1923,6 +1923,87 @@ def lists_i8_scan(codes, scales, d, members, offsets, qcodes, qscales, plan, npr
     return cand_scores, cand_ids
 
 
+# ------------------------------------------------------------------ inverted file, product-quantised lists (include/mdx_lists_pq.h)
+
+PQ_MAX_M = 128                    # include/mdx_lists_pq.h MDX_PQ_MAX_M: sub-quantisers of a code; a query's table is M KiB of LDS
+PQ_CODEWORDS = 256                # include/mdx_lists_pq.h MDX_PQ_CODEWORDS: a code is one byte
+
+
+def _pq_codewords(codewords, who):
+    """``codewords`` fp32 ``[M, 256, dsub]`` on the device, contiguous, checked; ``(M, dsub)``."""
+    _kmeans_tensor(codewords, torch.float32, who, "codewords", 3)
+    m, cw, dsub = codewords.shape
+    if cw != PQ_CODEWORDS or not 1 <= m <= PQ_MAX_M or not codewords.is_contiguous():
+        raise ValueError("%s: codewords must be a contiguous [M, %d, dsub] tensor with M in [1, %d], got %s"
+                         % (who, PQ_CODEWORDS, PQ_MAX_M, tuple(codewords.shape)))
+    return m, dsub
+
+
+def pq_lut(codewords, queries, qlayout="ND", center=None):
+    """fp32 ``[nq, M, 256]``: the look-up table of every query (``mdx_pq_lut``).  ``codewords`` fp32 ``[M, 256, dsub]`` on the device,
+    contiguous; ``queries`` fp32 ``[nq, M * dsub]`` (``"ND"``) or ``[M * dsub, nq]`` (``"DN"``), contiguous; ``center`` fp32
+    ``[M * dsub]`` or None (``x_q = q - center`` in one fp32 subtraction).  ``lut[q, m, j]`` is bit-identical to
+    ``DescriptorIndex(codewords[m], "ND").scores`` of sub-vector ``m`` of ``x_q`` at codeword ``j``."""
+    who = "pq_lut"
+    m, dsub = _pq_codewords(codewords, who)
+    _kmeans_tensor(queries, torch.float32, who, "queries", 2)
+    nq, dq, lay = _layout(queries, qlayout, "queries")
+    if dq != m * dsub:
+        raise ValueError("%s: query dimension %d != M * dsub = %d" % (who, dq, m * dsub))
+    if not queries.is_contiguous() or queries.device != codewords.device:
+        raise ValueError("%s: queries must be contiguous on %s" % (who, codewords.device))
+    cp = None
+    if center is not None:
+        cp = _ivf_vector(center, torch.float32, who, "center", (m * dsub,), codewords.device)
+    lut = torch.empty((nq, m, PQ_CODEWORDS), dtype=torch.float32, device=codewords.device)
+    with _on(codewords):
+        check(_lib.lib().mdx_pq_lut(_vp(codewords.data_ptr()), m, dsub, _vp(queries.data_ptr()), nq, lay, cp, _vp(lut.data_ptr()), _stream()),
+              "mdx_pq_lut")
+    return lut
+
+
+def lists_pq_scan(codes, members, n, offsets, lut, coarse, probes, plan, cap):
+    """``(cand_scores fp32 [nq, cap], cand_ids int64 [nq, cap])``: the ADC scores of every query against the members of the lists it
+    probes (``mdx_lists_pq_scan``), query-major, by look-ups in the query's table.  ``codes`` uint8 ``[m, M]`` on the device (rows
+    contiguous at any row stride): row ``p`` holds the code of row ``members[p]``; ``members`` int64 ``[m]``, ``n``: the rows the ids
+    refer to; ``offsets`` int64 ``[K + 1]``; ``lut`` fp32 ``[nq, M, 256]`` of :func:`pq_lut`; ``coarse`` fp32 and ``probes`` int64
+    ``[nq, nprobe]``: the values and ids of :func:`topk` over the centroid scores; ``plan``: :func:`ivf_plan` of the probes with the same
+    ``offsets``, ``m`` and ``cap``.  A candidate's column is the base of its probe plus its index in the list; its score is ``coarse``
+    plus the ``M`` table entries of its code, added in subspace order in fp32; columns at or beyond a query's count hold NaN / -1; a
+    member id outside ``[0, n)`` scores NaN."""
+    who = "lists_pq_scan"
+    _kmeans_tensor(codes, torch.uint8, who, "codes", 2)
+    m, sub = codes.shape
+    if not 1 <= sub <= PQ_MAX_M:
+        raise ValueError("%s: codes are [m, %d]: M must be in [1, %d]" % (who, sub, PQ_MAX_M))
+    if (sub > 1 and codes.stride(1) != 1) or (m > 1 and codes.stride(0) < sub):
+        raise ValueError("%s: codes must be a matrix with contiguous rows" % who)
+    ldc = codes.stride(0) if m > 1 else sub
+    _kmeans_tensor(lut, torch.float32, who, "lut", 3)
+    nq = lut.shape[0]
+    _ivf_vector(lut, torch.float32, who, "lut", (nq, sub, PQ_CODEWORDS), codes.device)
+    _kmeans_tensor(probes, torch.int64, who, "probes", 2)
+    nprobe = probes.shape[1]
+    _ivf_vector(probes, torch.int64, who, "probes", (nq, nprobe), codes.device)
+    _kmeans_tensor(coarse, torch.float32, who, "coarse", 2)
+    _ivf_vector(coarse, torch.float32, who, "coarse", (nq, nprobe), codes.device)
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    k = offsets.shape[0] - 1
+    _ivf_vector(members, torch.int64, who, "members", (m,), codes.device)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), codes.device)
+    for x, what in ((n, "n"), (cap, "cap")):
+        _ivf_count(x, who, what)
+    pp = _ivf_plan_arg(plan, who, nq, nprobe, k, codes.device)
+    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=codes.device)
+    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=codes.device)
+    with _on(codes):
+        check(_lib.lib().mdx_lists_pq_scan(_vp(codes.data_ptr()), m, sub, ldc, _vp(members.data_ptr()), n, _vp(offsets.data_ptr()), k,
+                                           _vp(lut.data_ptr()), _vp(coarse.data_ptr()), _vp(probes.data_ptr()), nq, nprobe, pp, plan.numel(),
+                                           cap, _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()), _stream()), "mdx_lists_pq_scan")
+    return cand_scores, cand_ids
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
