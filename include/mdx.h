@@ -1017,6 +1017,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * tests/test_gpu_lists_pq_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_lists_pq.h"
 
+/* ------------------------------------------- inverted file, editing the lists */
+
+/* Adding and removing rows after the build.  An index that keeps its rows in list order is three parts -- payload rows of opaque bytes,
+ * their member ids, the offsets of the lists -- and a batch of new rows, sorted by list, is a second structure of the same kind: adding
+ * it is the per-list concatenation of the two (mdx_lists_merge), removing rows the compaction of one along the prefix sum of its keep
+ * flags (mdx_lists_compact).  One gather pass each, no workspace.  The whole contract -- the structure, the order, the clamping, the
+ * widths of the loads and stores, the launch shape, the refusals -- is stated in mdx_lists_edit.h, beside this file, with the
+ * prototypes; their names are in _lib.LISTS_EDIT_EXPORTS, for the reason given above for mdx_knn_join.h, and their census is
+ * tests/test_lists_edit_host.py (every prototype is exported and bound; both have cases in tests/test_gpu_lists_edit_memcontract.py).
+ * Additions: MDX_ABI_VERSION stays. */
+#include "mdx_lists_edit.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

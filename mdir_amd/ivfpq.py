@@ -13,9 +13,10 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
     order, ``chunk`` rows at a time (default ``pq.CHUNK``).  ``codebook=None`` runs ``pq.train(residuals, m, **pq_train_kwargs)`` on all
     of them (a transient fp32 ``[N, D]`` block; ``N >= 256``); a :data:`pq.Codebook` is taken as it is.  ``codes`` uint8 ``[N, m]`` is
     ``pq.encode`` of the residuals: position ``p`` holds the code of row ``order[p]``.  With ``keep_rows=False`` the index drops its
-    reference to ``rows``.  Neither the labels nor the centroids are kept: ``order`` and ``offsets`` state the former, ``coarse`` holds
-    the latter.  ``nbytes()`` is what the index holds on the device: the codes, ``order``, ``offsets``, the codebook, the coarse
-    index, and the rows if they are kept.
+    reference to ``rows``.  The labels are not kept: ``order`` and ``offsets`` state them.  ``centroids`` stays referenced (it is the
+    caller's tensor; ``coarse`` holds its own copy).  ``nbytes()`` is what the index holds on the device: the codes, ``order``,
+    ``offsets``, the codebook, the coarse index, and the rows if they are kept -- the centroids are the caller's and are mirrored by
+    ``coarse``, so they are not counted a second time.
 
 ``IVFPQIndex.train(rows, lists, m=64, kmeans=None, pq=None, keep_rows=True)``
     ``cluster.kmeans(rows, lists, **kmeans)``, then the index of ``fit.centroids`` and ``fit.labels`` with ``**pq`` handed to
@@ -39,6 +40,45 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
     back and nothing synchronises.  There is no CPU fallback.
 
 ``index.close()`` releases the coarse index.
+
+After the build.  The index keeps a reference to the caller's ``centroids`` tensor (the residuals of a batch need it; ``coarse`` mirrors
+it in its own layout, so ``nbytes()`` does not count it a second time) and two numbers: ``index.n``, the id bound -- one more than the
+largest id ever issued -- and ``index.size``, the live rows, ``codes.shape[0]``.  They differ after a removal; the plan of a search
+takes ``size`` (offsets are clamped to the number of positions), the scan and the rescore padding ``n`` (the id bound).  A list's
+members ascend in id and new ids are larger than all old ones, so a batch is a small list-ordered structure of its own and adding it is
+a per-list concatenation (include/mdx_lists_edit.h; ``tests/lists_edit_restatement.py`` states the merge and the compaction in numpy).
+
+``index.add(batch, labels=None, chunk=None)`` -> ids int64 ``[B]``: ``n .. n + B - 1``
+    ``batch`` fp32 ``[B, D]`` on the index's device, rows contiguous; ``labels`` as for the constructor (``None``:
+    ``cluster.assign(index.centroids, batch, chunk)[0]``; explicit labels are range-checked with the one read-back the constructor
+    makes too).  1. ``cluster._members(labels, lists)`` of the batch; 2. the residuals of the batch in that order, ``chunk`` rows at a
+    time, by the expression of the constructor; 3. ``pq.encode`` with the index's codebook; 4. ``ops.lists_merge`` of the index's
+    structure with the batch's, whose members are ``n + batch_members``; 5. one read-back of the ``lists`` list sizes, for
+    ``host_sizes`` and ``capacity(.)``; 6. ``n += B`` and ``size += B``.  On any failure the index is left as it was.  Every step is
+    per row and independent of the chunk, so for any split of ``rows`` into consecutive batches the constructor on the first (with
+    ``codebook=`` given and ``keep_rows=False``) followed by ``add`` of the others has ``codes``, ``order``, ``offsets``, ``host_sizes``
+    and ``capacity(.)`` equal to those of the constructor on all of ``rows`` with the same centroids, codebook and labels (or ``None``):
+    every search result is equal bit for bit.  Every ``add`` rewrites the structure once, ``size (m + 8)`` bytes; there is no slack
+    capacity inside the lists.
+
+``index.remove(ids)`` -> the number of rows removed
+    ``ids`` int64 on the index's device, in any order; duplicates are allowed, and ids that are not live (negative, ``>= n``, already
+    removed) are ignored.  1. a dead flag per id in ``[0, n)``; 2. the keep flags of ``order``; 3. their exclusive prefix
+    (``torch.cumsum``); 4. one read-back of the new list sizes and the count (before the rows move, so that the result is allocated
+    at its size); 5. ``ops.lists_compact``.  Ids are never reused: ``n`` is unchanged and a later ``add`` continues at ``n``.  A removal
+    that would leave no row is a ``ValueError`` and changes nothing (the scan refuses ``m < 1``).
+
+``index.attach_rows(rows)``
+    For an index that does not keep the rows: ``rows`` fp32 ``[n, D]`` on the index's device, rows contiguous, becomes ``index.rows``,
+    so ``shortlist=`` works again; the rows at removed ids are never read.  ``attach_rows(None)`` drops the reference.  ``add`` and
+    ``remove`` on an index that currently keeps rows are a ``ValueError`` -- ``attach_rows(None)`` first: the index never copies or grows
+    the caller's tensor.
+
+``index.state()`` -> dict of ``centroids``, ``codewords``, ``codes``, ``order``, ``offsets`` (the index's own tensors, not copies), ``n``, ``m``
+``IVFPQIndex.from_state(state, device=None, rows=None)``
+    The index of a state: the tensors are moved to ``device`` (``None``: where the codes are), the coarse index and the capacities are
+    rebuilt from the centroids and the offsets (one read-back), ``rows`` goes to ``attach_rows``.  Its searches equal the original's bit
+    for bit.  Writing to disk is the caller's: ``torch.save(index.state(), path)``.
 """
 from collections import namedtuple
 
@@ -74,7 +114,7 @@ class IVFPQIndex:
         self.n, self.d, self.lists, self.m = partition.n, partition.d, partition.lists, m
         self.order, self.offsets, self.host_sizes = partition.order, partition.offsets, partition.host_sizes
         self._capacity, self.coarse, self.fit = partition._capacity, partition.coarse, None
-        self.device = rows.device
+        self.device, self.centroids, self.size = rows.device, centroids, partition.n
         try:
             step = min(self.n, chunk or _pq.CHUNK)
             if codebook is None:
@@ -96,9 +136,9 @@ class IVFPQIndex:
         self.codebook = codebook if isinstance(codebook, _pq.Codebook) else _pq.Codebook(codebook, [], 0)
         self.rows = rows if keep_rows else None
 
-    def _residuals(self, rows, centroids, labels, p0, p1):
-        """fp32 [p1 - p0, D]: row - centroids[label] of the rows at positions p0 .. p1 of the list order."""
-        ids = self.order[p0:p1]
+    def _residuals(self, rows, centroids, labels, p0, p1, order=None):
+        """fp32 [p1 - p0, D]: row - centroids[label] of the rows at positions p0 .. p1 of the list order (``order``: of a batch's)."""
+        ids = (self.order if order is None else order)[p0:p1]
         return rows.index_select(0, ids) - centroids.index_select(0, labels.index_select(0, ids))
 
     @classmethod
@@ -113,7 +153,8 @@ class IVFPQIndex:
         return index
 
     def nbytes(self):
-        """The bytes the index holds on the device: codes, order, offsets, codebook, coarse index, and the rows if they are kept."""
+        """The bytes the index holds on the device: codes, order, offsets, codebook, coarse index, and the rows if they are kept.  The
+        centroids are the caller's tensor and are mirrored by ``coarse``: they are not counted a second time."""
         held = self.codes.numel() + 8 * self.order.numel() + 8 * self.offsets.numel() + 4 * self.codebook.codewords.numel()
         held += self.coarse.device_bytes if self.coarse is not None else 0
         if self.rows is not None:
@@ -176,7 +217,7 @@ class IVFPQIndex:
         center = None if center is None else center.reshape(-1)
         probes, coarse = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
         cap = self.capacity(nprobe)
-        plan = ops.ivf_plan(probes, self.offsets, self.n, cap)
+        plan = ops.ivf_plan(probes, self.offsets, self.size, cap)    # the positions; self.n below is the id bound
         lut = ops.pq_lut(self.codebook.codewords, queries, qlayout, center)
         cand_scores, cand_ids = ops.lists_pq_scan(self.codes, self.order, self.n, self.offsets, lut, coarse, probes, plan, cap)
         ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k if shortlist is None else shortlist)
@@ -188,6 +229,144 @@ class IVFPQIndex:
         sure_ids, sure = ops.rescore(self.rows, queries, torch.where(ids < 0, self.n, ids), qlayout, center)
         sure_ids = torch.where(sure_ids >= self.n, -1, sure_ids)
         return IVFPQResult(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned)
+
+    # -------------------------------------------------------------------------------------------- after the build
+
+    @staticmethod
+    def _capacities(host_sizes):
+        capacity = [0]
+        for s in sorted(host_sizes, reverse=True):
+            capacity.append(capacity[-1] + s)
+        return capacity
+
+    def _check_edit(self, what):
+        if self.coarse is None:
+            raise ValueError("the index is closed")
+        if self.rows is not None:
+            raise ValueError("%s on an index that keeps the fp32 rows: the index never copies or grows the caller's tensor -- "
+                             "attach_rows(None) first" % what)
+
+    def add(self, batch, labels=None, chunk=None):
+        """Encodes ``batch`` (fp32 ``[B, D]``) and merges it into the lists; the ids int64 ``[B]`` it got, ``n .. n + B - 1`` -- the module
+        docstring has the contract."""
+        self._check_edit("add")
+        ivf._rows_matrix(batch, "batch")
+        b = batch.shape[0]
+        if batch.shape[1] != self.d:
+            raise ValueError("batch is [B, %d] and the index has D = %d" % (batch.shape[1], self.d))
+        if labels is not None:
+            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (b,):
+                raise ValueError("labels must be an int64 [%d] tensor, got %s" % (
+                    b, "%s %s" % (labels.dtype, tuple(labels.shape)) if isinstance(labels, torch.Tensor) else type(labels).__name__))
+        elif not batch.is_contiguous():
+            raise ValueError("batch must be contiguous to be assigned (labels=None)")
+        if chunk is not None:
+            cluster._count(chunk, "chunk")
+        if self.n + b >= 1 << 31:
+            raise ValueError("n + B = %d + %d ids: the id bound must stay below 2^31" % (self.n, b))
+        cluster._on_device(batch, "batch")
+        if batch.device != self.device:
+            raise ValueError("batch is on %s and the index on %s" % (batch.device, self.device))
+        if labels is not None:
+            cluster._on_device(labels, "labels")
+            if labels.device != self.device:
+                raise ValueError("labels are on %s and the index on %s" % (labels.device, self.device))
+            low, high = int(labels.min()), int(labels.max())
+            if low < 0 or high >= self.lists:
+                raise ValueError("labels must lie in [0, %d), got %d .. %d" % (self.lists, low, high))
+        else:
+            labels = cluster.assign(self.centroids, batch, chunk)[0]
+        members, offsets, _ = cluster._members(labels, self.lists)
+        step = min(b, chunk or _pq.CHUNK)
+        codes = torch.empty((b, self.m), dtype=torch.uint8, device=self.device)
+        for p0 in range(0, b, step):
+            codes[p0:p0 + step] = _pq.encode(self.codebook, self._residuals(batch, self.centroids, labels, p0, p0 + step, members))
+        merged = ops.lists_merge(self.codes, self.order, self.offsets, codes, members + self.n, offsets)
+        host_sizes = (merged[2][1:] - merged[2][:-1]).cpu().tolist()             # the one read-back
+        ids = torch.arange(self.n, self.n + b, dtype=torch.int64, device=self.device)
+        self.codes, self.order, self.offsets = merged
+        self.host_sizes, self._capacity = host_sizes, self._capacities(host_sizes)
+        self.n, self.size = self.n + b, self.size + b
+        return ids
+
+    def remove(self, ids):
+        """Drops the live rows among ``ids`` (int64 on the device; any order, duplicates and ids that are not live are ignored) from the
+        lists; the number of rows removed -- the module docstring has the contract."""
+        self._check_edit("remove")
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 1:
+            raise ValueError("ids must be an int64 1-d tensor, got %s" % (
+                "%s %s" % (ids.dtype, tuple(ids.shape)) if isinstance(ids, torch.Tensor) else type(ids).__name__))
+        cluster._on_device(ids, "ids")
+        if ids.device != self.device:
+            raise ValueError("ids are on %s and the index on %s" % (ids.device, self.device))
+        dead = torch.zeros(self.n + 1, dtype=torch.bool, device=self.device)       # entry n takes the ids that are out of range
+        dead.index_fill_(0, torch.where((ids >= 0) & (ids < self.n), ids, self.n), True)
+        kept = torch.zeros(self.size + 1, dtype=torch.int64, device=self.device)
+        kept[1:] = torch.cumsum(~dead.index_select(0, self.order), 0)
+        ends = kept.index_select(0, self.offsets)
+        *host_sizes, total = torch.cat([ends[1:] - ends[:-1], kept[-1:]]).cpu().tolist()        # the one read-back
+        if total < 1:
+            raise ValueError("removing these ids would leave no row in the index")
+        removed = self.size - total
+        if removed:
+            self.codes, self.order, self.offsets = ops.lists_compact(self.codes, self.order, self.offsets, kept, total)
+            self.host_sizes, self._capacity, self.size = host_sizes, self._capacities(host_sizes), total
+        return removed
+
+    def attach_rows(self, rows):
+        """``rows`` (fp32 ``[n, D]`` on the index's device, rows contiguous) becomes ``index.rows``, for ``shortlist=``; ``None`` drops the
+        reference."""
+        if rows is not None:
+            ivf._rows_matrix(rows, "rows")
+            if tuple(rows.shape) != (self.n, self.d):
+                raise ValueError("rows are %s and the ids of the index need [n = %d, D = %d]" % (tuple(rows.shape), self.n, self.d))
+            cluster._on_device(rows, "rows")
+            if rows.device != self.device:
+                raise ValueError("rows are on %s and the index on %s" % (rows.device, self.device))
+        self.rows = rows
+
+    def state(self):
+        """The index as plain tensors and numbers: ``centroids``, ``codewords``, ``codes``, ``order``, ``offsets`` (its own tensors, not
+        copies), ``n`` and ``m`` -- what :meth:`from_state` takes."""
+        return {"centroids": self.centroids, "codewords": self.codebook.codewords, "codes": self.codes, "order": self.order,
+                "offsets": self.offsets, "n": self.n, "m": self.m}
+
+    @classmethod
+    def from_state(cls, state, device=None, rows=None):
+        """The index of ``index.state()``, its tensors moved to ``device`` (``None``: where the codes are); ``rows`` as for
+        :meth:`attach_rows`."""
+        names = ("centroids", "codewords", "codes", "order", "offsets", "n", "m")
+        if not isinstance(state, dict) or any(name not in state for name in names):
+            raise ValueError("state must be a dict of %s" % ", ".join(names))
+        kinds = {"centroids": (torch.float32, 2), "codewords": (torch.float32, 3), "codes": (torch.uint8, 2), "order": (torch.int64, 1),
+                 "offsets": (torch.int64, 1)}
+        for name, (dtype, dims) in kinds.items():
+            t = state[name]
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != dims or t.numel() < 1:
+                raise ValueError("state[%r] must be a non-empty %d-d %s tensor" % (name, dims, dtype))
+        device = torch.device(state["codes"].device if device is None else device)
+        centroids, codewords, codes, order, offsets = (state[name].to(device).contiguous() for name in kinds)
+        n, m = state["n"], state["m"]
+        cluster._count(n, "n")
+        dsub = _pq._subspaces(m, centroids.shape[1])
+        _pq._codebook(codewords)
+        size, lists = codes.shape[0], centroids.shape[0]
+        if tuple(codewords.shape) != (m, _pq.CODEWORDS, dsub) or codes.shape[1] != m or tuple(order.shape) != (size,) \
+                or tuple(offsets.shape) != (lists + 1,) or size > n:
+            raise ValueError("the state does not fit together: centroids %s, codewords %s, codes %s, order %s, offsets %s, n = %d, m = %d" % (
+                tuple(centroids.shape), tuple(codewords.shape), tuple(codes.shape), tuple(order.shape), tuple(offsets.shape), n, m))
+        cluster._on_device(codes, "the state")
+        index = cls.__new__(cls)
+        index.n, index.size, index.d, index.lists, index.m = n, size, centroids.shape[1], lists, m
+        index.device, index.centroids, index.fit, index.rows = device, centroids, None, None
+        index.codes, index.order, index.offsets = codes, order, offsets
+        index.codebook = _pq.Codebook(codewords, [], 0)
+        index.host_sizes = (offsets[1:] - offsets[:-1]).cpu().tolist()             # the one read-back
+        index._capacity = cls._capacities(index.host_sizes)
+        index.coarse = None
+        index.attach_rows(rows)
+        index.coarse = ops.DescriptorIndex(centroids, "ND")
+        return index
 
     def close(self):
         """Releases the coarse index."""

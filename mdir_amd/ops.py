@@ -2004,6 +2004,99 @@ def lists_pq_scan(codes, members, n, offsets, lut, coarse, probes, plan, cap):
     return cand_scores, cand_ids
 
 
+# ------------------------------------------------------------------ inverted file, editing the lists (include/mdx_lists_edit.h)
+
+def _lists_structure(rows, members, offsets, who, which, device=None, may_be_empty=False):
+    """``(m, width, ld)`` of one list-ordered structure -- ``rows`` uint8 ``[m, width]`` with contiguous rows at any row stride,
+    ``members`` int64 ``[m]``, ``offsets`` int64 ``[K + 1]``, all on one device --, checked; a ValueError names what is wrong."""
+    for t, dtype, dims, what in ((rows, torch.uint8, 2, "rows"), (members, torch.int64, 1, "members"), (offsets, torch.int64, 1, "offsets")):
+        what = which + what
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("%s: %s must be a CUDA/ROCm tensor: the MI355X path has no CPU fallback" % (who, what))
+        if t.dtype != dtype or t.dim() != dims:
+            raise ValueError("%s: %s must be a %d-d %s tensor, got %s %s" % (who, what, dims, dtype, t.dtype, tuple(t.shape)))
+        if t.device != (device or rows.device):
+            raise ValueError("%s: %s is on %s, not on %s as the rows before it" % (who, what, t.device, device or rows.device))
+    m, width = rows.shape
+    if width < 1 or (m < 1 and not may_be_empty):
+        raise ValueError("%s: %srows must be a non-empty [m, width] tensor, got %s" % (who, which, tuple(rows.shape)))
+    if m and ((width > 1 and rows.stride(1) != 1) or (m > 1 and rows.stride(0) < width)):
+        raise ValueError("%s: %srows must be a matrix with contiguous rows" % (who, which))
+    if tuple(members.shape) != (m,) or not members.is_contiguous():
+        raise ValueError("%s: %smembers must be a contiguous [%d] tensor, got %s" % (who, which, m, tuple(members.shape)))
+    if offsets.shape[0] < 2 or not offsets.is_contiguous():
+        raise ValueError("%s: %soffsets must be a contiguous [K + 1] tensor with K >= 1, got %s" % (who, which, tuple(offsets.shape)))
+    return m, width, rows.stride(0) if m > 1 else width
+
+
+def _lists_outputs(who, out_rows, m, width, k, device):
+    """``(rows, ld, members, offsets)`` a call writes: ``out_rows`` as given (uint8 ``[m, width]``, contiguous rows at any row stride)
+    or a new contiguous block."""
+    if out_rows is None:
+        out_rows = torch.empty((m, width), dtype=torch.uint8, device=device)
+    else:
+        if not isinstance(out_rows, torch.Tensor) or not out_rows.is_cuda or out_rows.dtype != torch.uint8 or out_rows.device != device \
+                or tuple(out_rows.shape) != (m, width):
+            raise ValueError("%s: out_rows must be a uint8 [%d, %d] tensor on %s" % (who, m, width, device))
+        if (width > 1 and out_rows.stride(1) != 1) or (m > 1 and out_rows.stride(0) < width):
+            raise ValueError("%s: out_rows must be a matrix with contiguous rows" % who)
+    members = torch.empty((m,), dtype=torch.int64, device=device)
+    offsets = torch.empty((k + 1,), dtype=torch.int64, device=device)
+    return out_rows, (out_rows.stride(0) if m > 1 else width), members, offsets
+
+
+def lists_merge(a_rows, a_members, a_offsets, b_rows, b_members, b_offsets, out_rows=None):
+    """``(rows, members, offsets)``: per list the rows of structure ``a`` followed by those of structure ``b`` (``mdx_lists_merge``).  A
+    structure is ``rows`` uint8 ``[m, width]`` on the device (opaque payload; rows contiguous at any row stride), ``members`` int64
+    ``[m]`` and ``offsets`` int64 ``[K + 1]``; ``a`` and ``b`` share ``K`` and ``width``, and one of them may have no rows.  The result
+    has ``ma + mb`` rows, ``offsets = a_offsets + b_offsets`` (each clamped to its ``[0, m]``), rows and members moved together.
+    ``out_rows``: a uint8 ``[ma + mb, width]`` tensor to write the rows to (any row stride; the bytes between its rows stay as they
+    are) instead of a new one.  One pass, no temporary; nothing is read back."""
+    who = "lists_merge"
+    ma, width, a_ld = _lists_structure(a_rows, a_members, a_offsets, who, "a_", may_be_empty=True)
+    mb, width_b, b_ld = _lists_structure(b_rows, b_members, b_offsets, who, "b_", a_rows.device, may_be_empty=True)
+    if width_b != width or b_offsets.shape != a_offsets.shape:
+        raise ValueError("%s: a is [%d, %d] over %d lists and b [%d, %d] over %d: width and K must agree"
+                         % (who, ma, width, a_offsets.shape[0] - 1, mb, width_b, b_offsets.shape[0] - 1))
+    if ma + mb < 1:
+        raise ValueError("%s: neither structure has a row" % who)
+    k = a_offsets.shape[0] - 1
+    rows, out_ld, members, offsets = _lists_outputs(who, out_rows, ma + mb, width, k, a_rows.device)
+    # a structure of no rows has no storage: the other one's pointers stand in, and are never dereferenced
+    ar, am = (a_rows, a_members) if ma else (b_rows, b_members)
+    br, bm = (b_rows, b_members) if mb else (a_rows, a_members)
+    with _on(a_rows):
+        check(_lib.lib().mdx_lists_merge(_vp(ar.data_ptr()), a_ld, _vp(am.data_ptr()), _vp(a_offsets.data_ptr()), ma, _vp(br.data_ptr()), b_ld,
+                                         _vp(bm.data_ptr()), _vp(b_offsets.data_ptr()), mb, k, width, _vp(rows.data_ptr()), out_ld,
+                                         _vp(members.data_ptr()), _vp(offsets.data_ptr()), _stream()), "mdx_lists_merge")
+    return rows, members, offsets
+
+
+def lists_compact(rows, members, offsets, kept, total=None, out_rows=None):
+    """``(rows, members, offsets)``: the structure without the positions that are not kept (``mdx_lists_compact``).  ``rows``,
+    ``members``, ``offsets`` as in :func:`lists_merge`; ``kept`` int64 ``[m + 1]`` is the exclusive prefix sum of the keep flags:
+    position ``p`` is kept exactly when ``kept[p + 1] > kept[p]`` and goes to position ``kept[p]``; ``offsets`` becomes
+    ``kept[offsets]``.  The order inside a list is unchanged.  ``total``: the rows of the result, ``kept[m]`` -- ``None`` reads it
+    back (the one synchronisation; a caller that knows it passes it); it must be at least 1.  ``out_rows`` as in :func:`lists_merge`."""
+    who = "lists_compact"
+    m, width, ld = _lists_structure(rows, members, offsets, who, "")
+    if not isinstance(kept, torch.Tensor) or not kept.is_cuda or kept.dtype != torch.int64 or tuple(kept.shape) != (m + 1,) \
+            or not kept.is_contiguous() or kept.device != rows.device:
+        raise ValueError("%s: kept must be a contiguous int64 [%d] tensor on %s" % (who, m + 1, rows.device))
+    if total is None:
+        total = int(kept[m])
+    _ivf_count(total, who, "total")
+    if total > m:
+        raise ValueError("%s: total = %d > m = %d" % (who, total, m))
+    k = offsets.shape[0] - 1
+    out, out_ld, out_members, out_offsets = _lists_outputs(who, out_rows, total, width, k, rows.device)
+    with _on(rows):
+        check(_lib.lib().mdx_lists_compact(_vp(rows.data_ptr()), ld, _vp(members.data_ptr()), _vp(offsets.data_ptr()), m, k, width,
+                                           _vp(kept.data_ptr()), total, _vp(out.data_ptr()), out_ld, _vp(out_members.data_ptr()),
+                                           _vp(out_offsets.data_ptr()), _stream()), "mdx_lists_compact")
+    return out, out_members, out_offsets
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
