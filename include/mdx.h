@@ -1029,6 +1029,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * Additions: MDX_ABI_VERSION stays. */
 #include "mdx_lists_edit.h"
 
+/* ------------------------------- inverted file, int8 refinement of shortlists */
+
+/* A second-level code for the product-quantised lists: beside the M bytes of a position the MDX_I8 codes and the scale of its row -- the
+ * storage mdx_lists_i8_encode writes, opaque payload to mdx_lists_merge / mdx_lists_compact -- and a call that scores a per-query
+ * shortlist of ids against them and sorts it as mdx_rescore does.  An index then answers with int8-quality rankings and no fp32 rows
+ * on the device, and where the rows are attached the exact stage runs on a few hundred of them.  One gather pass over whole int8 rows
+ * and the per-query sort of mdx_rescore.  The whole contract -- the storage, the score to the bit, the order, the launch shape, the
+ * refusals -- is stated in mdx_refine.h, beside this file, with the prototypes; their names are in _lib.REFINE_EXPORTS, for the reason
+ * given above for mdx_knn_join.h, and their census is tests/test_refine_host.py (every prototype is exported and bound; the launching one
+ * has cases in tests/test_gpu_refine_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
+#include "mdx_refine.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

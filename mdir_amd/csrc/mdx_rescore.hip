@@ -6,10 +6,12 @@
 //                    flight in registers while wave 0 runs the chains (lane = candidate, the query chunk broadcast from
 //                    LDS).  The row loader, the stage arithmetic and the four-link chain step are those of mdx_exact.h, shared
 //                    with exact_kernel of mdx_join.hip: the bits are those of mdx_scores on an fp32 index of the same rows.
-//   rescore_sort     one workgroup per query: bitonic sort of up to 4096 (desc_key, id) pairs in LDS.
+//   rescore_sort     one workgroup per query: bitonic sort of up to 4096 (desc_key, id) pairs in LDS (mdx_shortlist_sort.h, shared
+//                    with mdx_refine.hip).
 //   certify_kernel   one workgroup per query: ||x_q||_1, the query's int8 scale, U_q and the certified depth.
 //   i8 bounds        a reduction over the codes and scales of an MDX_I8 shard (vector atomics of order-free max / min / or).
 #include "mdx_exact.h"
+#include "mdx_shortlist_sort.h"
 
 namespace mdx {
 namespace {
@@ -18,7 +20,6 @@ constexpr int RS_TC = 64;              // candidates per workgroup: one per lane
 constexpr int RS_KC = 256;             // k per stage: one 1-KiB piece of every row
 constexpr int RS_LD = RS_KC + 4;       // floats per LDS row: lane r reads row r with ds_read_b128, banks 4r .. 4r+3 (mod 64)
 constexpr int RS_ROWS_PER_WAVE = RS_TC / 4;
-constexpr int SORT_THREADS = 1024;
 
 // element k of query q (x_q = q - center, one fp32 subtraction), 0 beyond d
 __device__ __forceinline__ float query_elem(const float *queries, int64_t nq, int64_t d, int qlayout, const float *center,
@@ -87,53 +88,6 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float *__restrict__ 
         }
     }
     if (wave == 0 && c0 + lane < K) out[q * K + c0 + lane] = rid[lane] >= 0 ? acc : __builtin_nanf("");
-}
-
-// ascending (desc_key, id, position): key = desc_key << 32 | position, pads = ~0
-__device__ __forceinline__ bool sort_before(uint64_t a, uint64_t b, const int64_t *sid)
-{
-    if ((a >> 32) != (b >> 32)) return (a >> 32) < (b >> 32);
-    if (a == ~0ull || b == ~0ull) return a < b;
-    const int64_t ia = sid[a & 0xFFFFFFFFu], ib = sid[b & 0xFFFFFFFFu];
-    if (ia != ib) return ia < ib;
-    return a < b;
-}
-
-__global__ __launch_bounds__(SORT_THREADS) void rescore_sort_kernel(const float *__restrict__ sc, const int64_t *ids, int64_t K, int P,
-                                                                     int64_t *out_ids, float *out_scores)
-{
-    __shared__ uint64_t key[MDX_RESCORE_MAX_K];
-    __shared__ int64_t sid[MDX_RESCORE_MAX_K];
-    const int64_t q = blockIdx.x;
-    const int tid = threadIdx.x;
-    for (int i = tid; i < P; i += SORT_THREADS) {
-        if (i < K) {
-            key[i] = ((uint64_t)desc_key(sc[q * K + i]) << 32) | (uint32_t)i;
-            sid[i] = ids[q * K + i];
-        } else {
-            key[i] = ~0ull;
-        }
-    }
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = tid; i < P / 2; i += SORT_THREADS) {
-                const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const uint64_t a = key[lo], b = key[hi];
-                if (sort_before(b, a, sid) == up) {
-                    key[lo] = b;
-                    key[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < K; i += SORT_THREADS) {     // all of the query's ids are in LDS: out_ids may be ids
-        const uint32_t p = (uint32_t)(key[i] & 0xFFFFFFFFu);
-        out_ids[q * K + i] = sid[p];
-        out_scores[q * K + i] = sc[q * K + p];
-    }
 }
 
 // ---------------------------------------------------------------- the int8 shard's bounds

@@ -6,7 +6,7 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
 (include/mdx_lists_pq.h).  The fp32 rows are optional: they serve an exact second stage only.  Every result is defined to the bit;
 ``tests/pq_restatement.py`` states the search in numpy.
 
-``IVFPQIndex(rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, **pq_train_kwargs)``
+``IVFPQIndex(rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, refine=None, **pq_train_kwargs)``
     ``rows``, ``centroids``, ``labels`` and ``chunk`` as for ``ivf.IVFIndex``, which builds the partition: ``order``, ``offsets``, the
     list sizes on the host, ``capacity(nprobe)`` and ``coarse``, the fp32 index of the centroids, are its.  ``D % m == 0`` and
     ``1 <= m <= ops.PQ_MAX_M``.  The residuals ``r = row - centroids[label]`` (one fp32 subtraction per element) are taken in list
@@ -17,12 +17,17 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
     caller's tensor; ``coarse`` holds its own copy).  ``nbytes()`` is what the index holds on the device: the codes, ``order``,
     ``offsets``, the codebook, the coarse index, and the rows if they are kept -- the centroids are the caller's and are mirrored by
     ``coarse``, so they are not counted a second time.
+    ``refine=None`` is the index described so far.  ``refine="i8"`` (``D <= 133120``; any other value is a ``ValueError``) keeps a
+    second-level code beside the PQ codes (include/mdx_refine.h): ``refine_codes`` int8 ``[size, round_up(D, 64)]`` and
+    ``refine_scales`` fp32 ``[size]``, ``ops.lists_i8_encode(rows, order)`` -- the ``MDX_I8`` quantisation of the row at every position
+    -- and ``where`` int64 ``[n]``, the inverse of ``order`` with -1 at ids that are not live (derived: rebuilt after every change of
+    ``order``, never part of ``state()``).  ``nbytes()`` counts all three: about ``N (m + round_up(D, 64) + 20)`` bytes in all.
 
-``IVFPQIndex.train(rows, lists, m=64, kmeans=None, pq=None, keep_rows=True)``
+``IVFPQIndex.train(rows, lists, m=64, kmeans=None, pq=None, keep_rows=True, refine=None)``
     ``cluster.kmeans(rows, lists, **kmeans)``, then the index of ``fit.centroids`` and ``fit.labels`` with ``**pq`` handed to
     ``pq.train``; the :data:`cluster.KMeans` result stays reachable as ``.fit``.
 
-``index.search(queries, k, nprobe, qlayout="ND", center=None, shortlist=None)`` -> :data:`IVFPQResult`
+``index.search(queries, k, nprobe, qlayout="ND", center=None, shortlist=None, rescore=None)`` -> :data:`IVFPQResult`
     1. the coarse scores ``coarse.scores(queries, qlayout, center=center)``;
     2. ``ops.topk`` of them: ``probes`` and their values;
     3. ``ops.ivf_plan``;
@@ -34,10 +39,27 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
     ``keep_rows=True``) the ``S`` best by ADC score are rescored with ``ops.rescore`` on the fp32 rows and the first ``k`` returned:
     every returned score is the exact chain's bits, and where ``scanned[q] <= S`` the whole row, padding included, is that of
     ``ivf.IVFIndex(rows, centroids, labels).search``.  (The padding id goes to ``ops.rescore`` as the id ``N`` and comes back as -1, as
-    in ``ivf.py``.)  There is no certificate for the ADC shortlist.
+    in ``ivf.py``.)  There is no certificate for the ADC shortlist.  ``rescore`` other than ``None`` is a ``ValueError`` on such an
+    index.
+    On a ``refine="i8"`` index ``shortlist=None`` is the ADC ranking as above (``rescore`` must be ``None``), and with ``shortlist=S``:
+    ``rescore=None``  7. ``ops.quantize_i8(ops.center_rows(queries, qlayout, center))``: the query codes; 8. ``ops.refine_i8`` scores
+        the ``S`` best by ADC score on ``refine_codes`` and sorts them; the first ``k`` are returned.  No fp32 rows are needed.  The
+        padding goes in as the id ``n`` and comes back as -1, as above.
+    ``rescore=R`` (``k <= R <= S``; needs the fp32 rows, kept or attached)  9. the first ``R`` of the refined row go through
+        ``ops.rescore``; the first ``k`` are returned.  ``rescore=S`` is the rescoring of all of ``S`` in fp32.
+    What holds, and the tests check:
+    (a) every score returned with ``rescore=None`` is the bit pattern of ``DescriptorIndex(rows, "ND", storage="i8").scores(queries,
+        qlayout, center)`` at ``[q, id]``;
+    (b) where ``scanned[q] <= S`` the row equals the row of ``ivf.IVFIndex(rows, centroids, labels, storage="i8").search(queries, k,
+        nprobe, qlayout, center)`` -- ids, score bits and padding: both are the int8 ranking of the same candidates under the same
+        order, computed independently by the gather kernel here and the MFMA scan there;
+    (c) with ``rescore=R`` and ``scanned[q] <= R`` the row equals the fp32 ``ivf.IVFIndex`` search's row;
+    (d) every returned row is that of ``tests/refine_restatement.py`` bit for bit, whatever the query chunk.
+    There is no certificate for the refined shortlist either.
     The queries are taken ``query_chunk(nprobe, shortlist)`` at a time under ``ivf.CANDIDATE_MEMORY_CAP``; a query holds its candidate
-    row (12 bytes a column), its table (``m`` KiB) and, with a shortlist, ``28 S`` bytes.  The chunk changes no bit.  Nothing is read
-    back and nothing synchronises.  There is no CPU fallback.
+    row (12 bytes a column), its table (``m`` KiB) and, with a shortlist, ``28 S`` bytes -- on a ``refine="i8"`` index also its
+    centred row, codes and scale (``5 d + 4``) and the refined pairs (``16 S``).  The chunk changes no bit.  Nothing is read back
+    and nothing synchronises.  There is no CPU fallback.
 
 ``index.close()`` releases the coarse index.
 
@@ -59,14 +81,18 @@ a per-list concatenation (include/mdx_lists_edit.h; ``tests/lists_edit_restateme
     ``codebook=`` given and ``keep_rows=False``) followed by ``add`` of the others has ``codes``, ``order``, ``offsets``, ``host_sizes``
     and ``capacity(.)`` equal to those of the constructor on all of ``rows`` with the same centroids, codebook and labels (or ``None``):
     every search result is equal bit for bit.  Every ``add`` rewrites the structure once, ``size (m + 8)`` bytes; there is no slack
-    capacity inside the lists.
+    capacity inside the lists.  On a ``refine="i8"`` index the batch is also encoded with ``ops.lists_i8_encode(batch, members)`` and
+    ``refine_codes`` (as uint8 ``[size, round_up(D, 64)]``) and ``refine_scales`` (as uint8 ``[size, 4]``) go through the same
+    ``ops.lists_merge`` beside the PQ codes; the split-build guarantee extends to ``refine_codes``, ``refine_scales`` and ``where``
+    (same codebook, ``refine="i8"`` on both sides).
 
 ``index.remove(ids)`` -> the number of rows removed
     ``ids`` int64 on the index's device, in any order; duplicates are allowed, and ids that are not live (negative, ``>= n``, already
     removed) are ignored.  1. a dead flag per id in ``[0, n)``; 2. the keep flags of ``order``; 3. their exclusive prefix
     (``torch.cumsum``); 4. one read-back of the new list sizes and the count (before the rows move, so that the result is allocated
     at its size); 5. ``ops.lists_compact``.  Ids are never reused: ``n`` is unchanged and a later ``add`` continues at ``n``.  A removal
-    that would leave no row is a ``ValueError`` and changes nothing (the scan refuses ``m < 1``).
+    that would leave no row is a ``ValueError`` and changes nothing (the scan refuses ``m < 1``).  On a ``refine="i8"`` index
+    ``refine_codes`` and ``refine_scales`` are compacted with the same ``kept`` and ``where`` is rebuilt.
 
 ``index.attach_rows(rows)``
     For an index that does not keep the rows: ``rows`` fp32 ``[n, D]`` on the index's device, rows contiguous, becomes ``index.rows``,
@@ -78,7 +104,9 @@ a per-list concatenation (include/mdx_lists_edit.h; ``tests/lists_edit_restateme
 ``IVFPQIndex.from_state(state, device=None, rows=None)``
     The index of a state: the tensors are moved to ``device`` (``None``: where the codes are), the coarse index and the capacities are
     rebuilt from the centroids and the offsets (one read-back), ``rows`` goes to ``attach_rows``.  Its searches equal the original's bit
-    for bit.  Writing to disk is the caller's: ``torch.save(index.state(), path)``.
+    for bit.  Writing to disk is the caller's: ``torch.save(index.state(), path)``.  The state of a ``refine="i8"`` index also holds
+    ``refine_codes`` and ``refine_scales``; ``from_state`` checks their dtypes and shapes against ``codes`` and ``centroids``, rebuilds
+    ``where`` and gives a ``refine="i8"`` index.  A state without those keys loads as a ``refine=None`` index.
 """
 from collections import namedtuple
 
@@ -92,15 +120,28 @@ its candidates) -- ADC scores without a shortlist, exact chain scores with one; 
 first; scanned int64 [nq]: its candidates."""
 
 
+REFINES = (None, "i8")
+
+
+def _check_refine(refine, d):
+    if refine is not None and not (isinstance(refine, str) and refine in REFINES):
+        raise ValueError("refine must be None or \"i8\", got %r" % (refine,))
+    if refine == "i8" and d > ops.LISTS_I8_MAX_D:
+        raise ValueError("refine=\"i8\": D = %d > %d" % (d, ops.LISTS_I8_MAX_D))
+
+
 class IVFPQIndex:
     """The inverted file of the product-quantised residuals of ``rows`` over ``centroids`` -- the module docstring states the
     contract."""
 
-    def __init__(self, rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, **pq_train_kwargs):
+    refine = None              # "i8": refine_codes, refine_scales and where are kept
+
+    def __init__(self, rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, refine=None, **pq_train_kwargs):
         ivf._rows_matrix(rows, "rows")
         dsub = _pq._subspaces(m, rows.shape[1])
         if not isinstance(keep_rows, bool):
             raise ValueError("keep_rows must be a bool, got %r" % (keep_rows,))
+        _check_refine(refine, rows.shape[1])
         if codebook is not None:
             if pq_train_kwargs:
                 raise ValueError("a codebook is given: %s would not be used" % sorted(pq_train_kwargs))
@@ -130,6 +171,10 @@ class IVFPQIndex:
                 self.codes = torch.empty((self.n, m), dtype=torch.uint8, device=self.device)
                 for p0 in range(0, self.n, step):
                     self.codes[p0:p0 + step] = _pq.encode(codebook, self._residuals(rows, centroids, partition.labels, p0, p0 + step))
+            if refine is not None:
+                self.refine = refine
+                self.refine_codes, self.refine_scales = ops.lists_i8_encode(rows, self.order)
+                self.where = self._where()
         except BaseException:
             self.close()
             raise
@@ -141,22 +186,32 @@ class IVFPQIndex:
         ids = (self.order if order is None else order)[p0:p1]
         return rows.index_select(0, ids) - centroids.index_select(0, labels.index_select(0, ids))
 
+    def _where(self):
+        """int64 [n]: the position of every live id in the list order, -1 at ids that are not live -- the inverse of ``order``."""
+        where = torch.full((self.n,), -1, dtype=torch.int64, device=self.device)
+        where.index_copy_(0, self.order, torch.arange(self.size, dtype=torch.int64, device=self.device))
+        return where
+
     @classmethod
-    def train(cls, rows, lists, m=64, kmeans=None, pq=None, keep_rows=True):
+    def train(cls, rows, lists, m=64, kmeans=None, pq=None, keep_rows=True, refine=None):
         """The index of ``cluster.kmeans(rows, lists, **kmeans)`` with ``pq.train(residuals, m, **pq)``; the fit stays reachable as
         ``.fit``."""
         ivf._rows_matrix(rows, "rows")
         _pq._subspaces(m, rows.shape[1])
+        _check_refine(refine, rows.shape[1])
         fit = cluster.kmeans(rows, lists, **(kmeans or {}))
-        index = cls(rows, fit.centroids, fit.labels, m=m, keep_rows=keep_rows, **(pq or {}))
+        index = cls(rows, fit.centroids, fit.labels, m=m, keep_rows=keep_rows, refine=refine, **(pq or {}))
         index.fit = fit
         return index
 
     def nbytes(self):
-        """The bytes the index holds on the device: codes, order, offsets, codebook, coarse index, and the rows if they are kept.  The
-        centroids are the caller's tensor and are mirrored by ``coarse``: they are not counted a second time."""
+        """The bytes the index holds on the device: codes, order, offsets, codebook, coarse index, the refinement codes, scales and
+        ``where`` of a ``refine="i8"`` index, and the rows if they are kept.  The centroids are the caller's tensor and are mirrored by
+        ``coarse``: they are not counted a second time."""
         held = self.codes.numel() + 8 * self.order.numel() + 8 * self.offsets.numel() + 4 * self.codebook.codewords.numel()
         held += self.coarse.device_bytes if self.coarse is not None else 0
+        if self.refine is not None:
+            held += self.refine_codes.numel() + 4 * self.refine_scales.numel() + 8 * self.where.numel()
         if self.rows is not None:
             held += 4 * self.rows.shape[0] * (self.rows.stride(0) if self.rows.shape[0] > 1 else self.rows.shape[1])
         return held
@@ -167,22 +222,35 @@ class IVFPQIndex:
 
     def query_chunk(self, nprobe, shortlist=None):
         """Queries per step of ``search``: as many as keep their candidate rows (12 bytes a column), their tables (``m`` KiB each) and,
-        with a shortlist of ``S``, the selection and the rescored pairs (``28 S``) under ``ivf.CANDIDATE_MEMORY_CAP`` (at least one)."""
+        with a shortlist of ``S``, the selection and the rescored pairs (``28 S``) under ``ivf.CANDIDATE_MEMORY_CAP`` (at least one).  On a
+        ``refine="i8"`` index a shortlisted query also holds its centred row, codes and scale (``5 d + 4`` bytes) and the refined pairs
+        with their unsorted scores (``16 S``)."""
         per_query = 12 * self.capacity(nprobe) + 4 * _pq.CODEWORDS * self.m + (0 if shortlist is None else 28 * shortlist)
+        if self.refine is not None and shortlist is not None:
+            per_query += 5 * self.d + 4 + 16 * shortlist
         return max(1, ivf.CANDIDATE_MEMORY_CAP // per_query)
 
-    def _check_search(self, queries, k, nprobe, qlayout, center, shortlist):
+    def _check_search(self, queries, k, nprobe, qlayout, center, shortlist, rescore=None):
         if self.coarse is None:
             raise ValueError("the index is closed")
         cluster._count(k, "k")
         if k > ops.RESCORE_MAX_K:
             raise ValueError("k = %d > %d" % (k, ops.RESCORE_MAX_K))
+        if rescore is not None and self.refine is None:
+            raise ValueError("rescore = %r needs an index built with refine=\"i8\"" % (rescore,))
         if shortlist is not None:
             cluster._count(shortlist, "shortlist")
             if not k <= shortlist <= ops.RESCORE_MAX_K:
                 raise ValueError("shortlist = %d must be in [k = %d, %d]" % (shortlist, k, ops.RESCORE_MAX_K))
-            if self.rows is None:
-                raise ValueError("a shortlist is rescored on the fp32 rows; this index was built with keep_rows=False")
+            if rescore is not None:
+                cluster._count(rescore, "rescore")
+                if not k <= rescore <= shortlist:
+                    raise ValueError("rescore = %d must be in [k = %d, shortlist = %d]" % (rescore, k, shortlist))
+            if self.rows is None and (self.refine is None or rescore is not None):
+                raise ValueError("%s is rescored on the fp32 rows; this index was built with keep_rows=False" % (
+                    "a shortlist" if self.refine is None else "rescore = %d of the refined shortlist" % rescore))
+        elif rescore is not None:
+            raise ValueError("rescore = %r needs a shortlist" % (rescore,))
         if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32 or queries.dim() != 2 or queries.numel() < 1:
             raise ValueError("queries must be a non-empty fp32 2-d tensor, got %s" % (
                 "%s %s" % (queries.dtype, tuple(queries.shape)) if isinstance(queries, torch.Tensor) else type(queries).__name__))
@@ -205,14 +273,15 @@ class IVFPQIndex:
         if center is not None and center.device != self.device:
             raise ValueError("center is on %s and the index on %s" % (center.device, self.device))
 
-    def search(self, queries, k, nprobe, qlayout="ND", center=None, shortlist=None):
+    def search(self, queries, k, nprobe, qlayout="ND", center=None, shortlist=None, rescore=None):
         """:data:`IVFPQResult` of the ``k`` best rows of every query among the members of its ``nprobe`` best lists, by ADC score or,
-        with a shortlist, by the exact score of the ADC shortlist -- the module docstring has the contract."""
-        self._check_search(queries, k, nprobe, qlayout, center, shortlist)
+        with a shortlist, by the exact score of the ADC shortlist -- on a ``refine="i8"`` index by its int8 score, and with ``rescore=R``
+        by the exact score of the ``R`` best of those -- the module docstring has the contract."""
+        self._check_search(queries, k, nprobe, qlayout, center, shortlist, rescore)
         return ivf.IVFIndex._chunked(self, self._search, IVFPQResult, self.query_chunk(nprobe, shortlist), queries, qlayout, k, nprobe,
-                                     center, shortlist)
+                                     center, shortlist, rescore)
 
-    def _search(self, queries, qlayout, k, nprobe, center, shortlist):
+    def _search(self, queries, qlayout, k, nprobe, center, shortlist, rescore=None):
         nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
         center = None if center is None else center.reshape(-1)
         probes, coarse = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
@@ -226,7 +295,15 @@ class IVFPQIndex:
             return IVFPQResult(ids, scores, probes, scanned)
         del cand_scores, cand_ids, lut
         # the padding of a shortlist as the id n: not dereferenced, NaN, and behind every candidate in the order of the rescored row
-        sure_ids, sure = ops.rescore(self.rows, queries, torch.where(ids < 0, self.n, ids), qlayout, center)
+        ids = torch.where(ids < 0, self.n, ids)
+        if self.refine is not None:
+            qcodes, qscales = ops.quantize_i8(ops.center_rows(queries, qlayout, center))
+            ids, fine = ops.refine_i8(self.refine_codes, self.refine_scales, self.d, self.where, qcodes, qscales, ids)
+            if rescore is None:
+                ids = torch.where(ids >= self.n, -1, ids)
+                return IVFPQResult(ids[:, :k].contiguous(), fine[:, :k].contiguous(), probes, scanned)
+            ids = ids[:, :rescore].contiguous()
+        sure_ids, sure = ops.rescore(self.rows, queries, ids, qlayout, center)
         sure_ids = torch.where(sure_ids >= self.n, -1, sure_ids)
         return IVFPQResult(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned)
 
@@ -282,11 +359,19 @@ class IVFPQIndex:
         for p0 in range(0, b, step):
             codes[p0:p0 + step] = _pq.encode(self.codebook, self._residuals(batch, self.centroids, labels, p0, p0 + step, members))
         merged = ops.lists_merge(self.codes, self.order, self.offsets, codes, members + self.n, offsets)
+        if self.refine is not None:                                               # the same merge of the two other payloads, as bytes
+            fine_codes, fine_scales = ops.lists_i8_encode(batch, members)
+            fine = [ops.lists_merge(mine.view(torch.uint8).view(self.size, -1), self.order, self.offsets,
+                                    new.view(torch.uint8).view(b, -1), members + self.n, offsets)[0]
+                    for mine, new in ((self.refine_codes, fine_codes), (self.refine_scales, fine_scales))]
         host_sizes = (merged[2][1:] - merged[2][:-1]).cpu().tolist()             # the one read-back
         ids = torch.arange(self.n, self.n + b, dtype=torch.int64, device=self.device)
         self.codes, self.order, self.offsets = merged
         self.host_sizes, self._capacity = host_sizes, self._capacities(host_sizes)
         self.n, self.size = self.n + b, self.size + b
+        if self.refine is not None:
+            self.refine_codes, self.refine_scales = fine[0].view(torch.int8), fine[1].view(torch.float32).view(self.size)
+            self.where = self._where()
         return ids
 
     def remove(self, ids):
@@ -309,8 +394,14 @@ class IVFPQIndex:
             raise ValueError("removing these ids would leave no row in the index")
         removed = self.size - total
         if removed:
+            if self.refine is not None:
+                fine = [ops.lists_compact(mine.view(torch.uint8).view(self.size, -1), self.order, self.offsets, kept, total)[0]
+                        for mine in (self.refine_codes, self.refine_scales)]
             self.codes, self.order, self.offsets = ops.lists_compact(self.codes, self.order, self.offsets, kept, total)
             self.host_sizes, self._capacity, self.size = host_sizes, self._capacities(host_sizes), total
+            if self.refine is not None:
+                self.refine_codes, self.refine_scales = fine[0].view(torch.int8), fine[1].view(torch.float32).view(total)
+                self.where = self._where()
         return removed
 
     def attach_rows(self, rows):
@@ -327,9 +418,13 @@ class IVFPQIndex:
 
     def state(self):
         """The index as plain tensors and numbers: ``centroids``, ``codewords``, ``codes``, ``order``, ``offsets`` (its own tensors, not
-        copies), ``n`` and ``m`` -- what :meth:`from_state` takes."""
-        return {"centroids": self.centroids, "codewords": self.codebook.codewords, "codes": self.codes, "order": self.order,
-                "offsets": self.offsets, "n": self.n, "m": self.m}
+        copies), ``n`` and ``m`` -- and ``refine_codes`` and ``refine_scales`` of a ``refine="i8"`` index -- what :meth:`from_state`
+        takes."""
+        state = {"centroids": self.centroids, "codewords": self.codebook.codewords, "codes": self.codes, "order": self.order,
+                 "offsets": self.offsets, "n": self.n, "m": self.m}
+        if self.refine is not None:
+            state.update(refine_codes=self.refine_codes, refine_scales=self.refine_scales)
+        return state
 
     @classmethod
     def from_state(cls, state, device=None, rows=None):
@@ -355,11 +450,23 @@ class IVFPQIndex:
                 or tuple(offsets.shape) != (lists + 1,) or size > n:
             raise ValueError("the state does not fit together: centroids %s, codewords %s, codes %s, order %s, offsets %s, n = %d, m = %d" % (
                 tuple(centroids.shape), tuple(codewords.shape), tuple(codes.shape), tuple(order.shape), tuple(offsets.shape), n, m))
+        fine = [state.get(name) for name in ("refine_codes", "refine_scales")]
+        if any(t is not None for t in fine):
+            d_pad = (centroids.shape[1] + 63) // 64 * 64
+            for t, name, dtype, shape in zip(fine, ("refine_codes", "refine_scales"), (torch.int8, torch.float32), ((size, d_pad), (size,))):
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+                    raise ValueError("state[%r] must be a %s tensor of shape %s beside codes %s and centroids %s" % (
+                        name, dtype, list(shape), tuple(codes.shape), tuple(centroids.shape)))
+            _check_refine("i8", centroids.shape[1])
         cluster._on_device(codes, "the state")
         index = cls.__new__(cls)
+        if fine[0] is not None:
+            index.refine, index.refine_codes, index.refine_scales = "i8", fine[0].to(device).contiguous(), fine[1].to(device).contiguous()
         index.n, index.size, index.d, index.lists, index.m = n, size, centroids.shape[1], lists, m
         index.device, index.centroids, index.fit, index.rows = device, centroids, None, None
         index.codes, index.order, index.offsets = codes, order, offsets
+        if index.refine is not None:
+            index.where = index._where()
         index.codebook = _pq.Codebook(codewords, [], 0)
         index.host_sizes = (offsets[1:] - offsets[:-1]).cpu().tolist()             # the one read-back
         index._capacity = cls._capacities(index.host_sizes)

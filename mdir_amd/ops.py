@@ -2097,6 +2097,44 @@ def lists_compact(rows, members, offsets, kept, total=None, out_rows=None):
     return out, out_members, out_offsets
 
 
+# ------------------------------------------------------------------ inverted file, int8 refinement of shortlists (include/mdx_refine.h)
+
+def refine_i8(codes, scales, d, where, qcodes, qscales, ids):
+    """``(ids int64 [nq, S], scores fp32 [nq, S])``: the ``MDX_I8`` scores of each query's shortlist ``ids`` (int64 ``[nq, S]``,
+    ``S <= RESCORE_MAX_K``) against the storage of :func:`lists_i8_encode`, sorted as :func:`rescore` sorts (``mdx_refine_i8``).
+    ``codes`` int8 ``[m, round_up(d, 64)]`` and ``scales`` fp32 ``[m]``; ``d``: the dimension of the rows; ``where`` int64 ``[n]``: the
+    position in ``[0, m)`` that holds id ``i`` (any other value: the id is not stored); ``qcodes`` int8 ``[nq, d]`` and ``qscales`` fp32
+    ``[nq]`` are ``quantize_i8(center_rows(queries, qlayout, center))``.  Every score is bit-identical to
+    ``DescriptorIndex(rows, "ND", storage="i8").scores(queries, qlayout, center)`` at the same id; an id outside ``[0, n)`` or one that
+    is not stored is never dereferenced, scores NaN and sorts last."""
+    who = "refine_i8"
+    cp, sp, m = _lists_i8_storage(codes, scales, d, who)
+    _kmeans_tensor(where, torch.int64, who, "where", 1)
+    n = where.shape[0]
+    _ivf_vector(where, torch.int64, who, "where", (n,), codes.device)
+    _kmeans_tensor(qcodes, torch.int8, who, "qcodes", 2)
+    nq, dq = qcodes.shape
+    if dq != d:
+        raise ValueError("%s: query dimension %d != rows dimension %d" % (who, dq, d))
+    _ivf_vector(qcodes, torch.int8, who, "qcodes", (nq, d), codes.device)
+    _kmeans_tensor(qscales, torch.float32, who, "qscales", 1)
+    _ivf_vector(qscales, torch.float32, who, "qscales", (nq,), codes.device)
+    _kmeans_tensor(ids, torch.int64, who, "ids", 2)
+    if ids.shape[0] != nq or not 1 <= ids.shape[1] <= RESCORE_MAX_K:
+        raise ValueError("%s: ids must be [%d, S] with S in [1, %d], got %s" % (who, nq, RESCORE_MAX_K, tuple(ids.shape)))
+    s = ids.shape[1]
+    _ivf_vector(ids, torch.int64, who, "ids", (nq, s), codes.device)
+    out_ids = torch.empty((nq, s), dtype=torch.int64, device=codes.device)
+    out_scores = torch.empty((nq, s), dtype=torch.float32, device=codes.device)
+    h = _lib.lib()
+    ws = _workspace(h.mdx_refine_i8_workspace(nq, s), codes.device)
+    with _on(codes):
+        check(h.mdx_refine_i8(cp, sp, m, d, _vp(where.data_ptr()), n, _vp(qcodes.data_ptr()), _vp(qscales.data_ptr()), nq,
+                              _vp(ids.data_ptr()), s, _vp(out_ids.data_ptr()), _vp(out_scores.data_ptr()), _vp(ws.data_ptr()), ws.numel(),
+                              _stream()), "mdx_refine_i8")
+    return out_ids, out_scores
+
+
 def _csr(id_lists, device):
     arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
