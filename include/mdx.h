@@ -1041,6 +1041,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * has cases in tests/test_gpu_refine_memcontract.py).  Additions: MDX_ABI_VERSION stays. */
 #include "mdx_refine.h"
 
+/* ------------------------------- kNN lists, reverse-edge merge */
+
+/* The kNN lists of all rows, improved by their own reverse edges: the exact chain is symmetric to the bit, so where row i lists j and
+ * j does not list i, the pair (i, score) is offered to j at no scoring cost, and every row keeps the first k of its own entries and its
+ * offers.  This is what makes an approximate join through the inverted file (mdir_amd/ivf.py, IVFIndex.knn_join) as good as a wider
+ * probe.  A count pass, the caller's prefix sum, a fill pass and a one-wave-per-row merge.  The whole contract -- the definition, the
+ * order, the determinism, the offer buffer, the launch shape, the refusals -- is stated in mdx_knn_reverse.h, beside this file, with
+ * the prototypes; their names are in _lib.KNN_REVERSE_EXPORTS, for the reason given above for mdx_knn_join.h, and their census is
+ * tests/test_knn_reverse_host.py (every prototype is exported and bound; each has cases in tests/test_gpu_knn_reverse_memcontract.py).
+ * Additions: MDX_ABI_VERSION stays. */
+#include "mdx_knn_reverse.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -55,6 +55,32 @@ rows, with fewer probes it is that ranking restricted to the rows of the probed 
     is the one read-back of a search: ``nonzero`` of ``certified < k``.  ``shortlist`` and ``exact`` are a ``ValueError`` on an
     ``"f32"`` index.  ``query_chunk(nprobe, shortlist)`` counts the query codes and the shortlist's buffers as well.
 
+``index.knn_join(k, nprobe, shortlist=None, reverse=True, chunk=None)`` -> :data:`IVFKnnResult`
+    The approximate kNN join of the rows with themselves, ``k' = min(k, N)`` neighbours a row, for the database-side re-ranking
+    (``rerank.database_augmentation``, ``rerank.DiffusionGraph``, ``rerank.ReciprocalEncoding``), whose exact lists
+    (``search.knn_join``) cost a pass over all pairs.
+    Forward stage: ``self.search(rows[lo:hi], k', nprobe, shortlist=shortlist)`` for blocks of ``chunk`` rows (a contiguous copy of the
+    block where the rows are strided); ``ids``, ``scores`` and ``scanned`` are kept, the probes dropped.  The forward lists are, by
+    definition and to the bit, ``index.search(rows, k', nprobe, shortlist=shortlist)``, and ``chunk`` changes nothing.  The default
+    chunk is ``min(query_chunk(nprobe, shortlist), 32768)``: ``search`` then takes a block in one step, its candidate buffers stay under
+    ``CANDIDATE_MEMORY_CAP``, and the ``[chunk, lists]`` coarse scores, which that cap does not count, under half a GiB at 4096 lists.
+    On an ``"i8"`` index ``shortlist`` is required (a ``ValueError`` without one): every returned score is then the exact chain's bits,
+    which is also what the symmetry premise of the reverse stage needs.  On an ``"f32"`` index ``shortlist`` is refused, as ``search``
+    refuses it.  After the forward stage there is one read-back, ``scanned.min()``: a row that scanned fewer than ``k'`` candidates is
+    a ``ValueError`` that names ``nprobe`` (the graph kernels downstream are not specified on padded lists).
+    Reverse stage (``reverse=True``; ``k' <= ops.KNN_REVERSE_MAX_K``, else a ``ValueError``): ``ops.knn_reverse_merge`` of the whole
+    ``[N, k']`` result -- the chain is symmetric to the bit, so where i found j and j did not find i, i is offered to j at no scoring
+    cost; ``gained[j]`` counts the entries row j took from such offers.  With ``reverse=False`` ``gained`` is zeros.
+    A row's own match is present whenever its own list is among its probes.  That always holds for ``labels=None`` and for
+    ``IVFIndex.train``, where a row's list is the argmax of the same coarse scores its probes are the top of; explicit labels can
+    break it.
+    With ``nprobe == lists`` the result is ``search.knn_join(None, rows, k)`` bit for bit and ``gained`` is all zero (on an ``"i8"``
+    index this needs ``shortlist >= N``).
+
+``IVFNeighbours(index, nprobe, shortlist=None, reverse=True)``
+    What the re-ranking code carries in place of an int8 ``DescriptorIndex``: ``rerank`` calls ``index.knn_join(k, nprobe, shortlist,
+    reverse)`` for its neighbour lists, after checking that its ``vecs`` are the index's ``rows``.
+
 ``index.close()`` releases the coarse index.
 """
 from collections import namedtuple
@@ -71,7 +97,13 @@ IVFRescored = namedtuple("IVFRescored", ["ids", "scores", "probes", "scanned", "
 IVFRescored.__doc__ = """ids, scores, probes, scanned as in :data:`IVFResult`; certified int64 [nq]: the leading entries that are, bit for
 bit, the fp32 index's (None without a shortlist); fallback int64 [f]: the queries answered by the fp32 scan (empty unless exact=True)."""
 
+IVFKnnResult = namedtuple("IVFKnnResult", ["ids", "scores", "scanned", "gained"])
+IVFKnnResult.__doc__ = """ids int64 [N, k'] and scores fp32 [N, k'] (k' = min(k, N)): the neighbour list of every row, best first;
+scanned int64 [N]: the candidates of its forward search; gained int32 [N]: the entries it took from reverse edges."""
+
 STORAGES = ("f32", "i8")
+
+KNN_JOIN_CHUNK = 1 << 15          # the most rows per block of knn_join by default: the [chunk, lists] coarse scores stay small
 
 CANDIDATE_MEMORY_CAP = 4 << 30    # bytes of candidate scores and ids ([chunk, capacity] fp32 + int64) one step of search may hold
 
@@ -268,11 +300,78 @@ class IVFIndex:
         certified = torch.where(scanned <= shortlist, shortlist, depth.to(torch.int64))
         return IVFRescored(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned, certified, none)
 
+    def knn_join(self, k, nprobe, shortlist=None, reverse=True, chunk=None):
+        """:data:`IVFKnnResult`: the ``min(k, N)`` best rows of every row among the members of its ``nprobe`` best lists, merged with
+        their reverse edges -- the module docstring has the contract."""
+        cluster._count(k, "k")
+        k = min(k, self.n)
+        if not isinstance(reverse, bool):
+            raise ValueError("reverse must be a bool, got %r" % (reverse,))
+        if chunk is not None:
+            cluster._count(chunk, "chunk")
+        if self.storage == "i8" and shortlist is None:
+            raise ValueError("knn_join on an int8 index needs a shortlist: its scores are then the exact chain's, which the reverse "
+                             "merge and the re-ranking rest on")
+        self._check_stages(k, shortlist, False)
+        if reverse and k > ops.KNN_REVERSE_MAX_K:
+            raise ValueError("knn_join: k = %d > %d with reverse=True (ops.KNN_REVERSE_MAX_K)" % (k, ops.KNN_REVERSE_MAX_K))
+        cluster._count(nprobe, "nprobe")
+        if nprobe > self.lists:
+            raise ValueError("nprobe = %d > %d lists" % (nprobe, self.lists))
+        if self.coarse is None:
+            raise ValueError("the index is closed")
+        if chunk is None:
+            chunk = min(self.query_chunk(nprobe, shortlist), KNN_JOIN_CHUNK)
+        n, device = self.n, self.rows.device
+        ids = torch.empty((n, k), dtype=torch.int64, device=device)
+        scores = torch.empty((n, k), dtype=torch.float32, device=device)
+        scanned = torch.empty((n,), dtype=torch.int64, device=device)
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            res = self.search(self.rows[lo:hi].contiguous(), k, nprobe, shortlist=shortlist)
+            ids[lo:hi], scores[lo:hi], scanned[lo:hi] = res.ids, res.scores, res.scanned
+            del res
+        least = int(scanned.min())                                              # the one read-back
+        if least < k:
+            raise ValueError("knn_join: a row scanned %d candidates, fewer than k = %d: nprobe = %d is too small for these lists"
+                             % (least, k, nprobe))
+        if not reverse:
+            return IVFKnnResult(ids, scores, scanned, torch.zeros((n,), dtype=torch.int32, device=device))
+        ids, scores, gained = ops.knn_reverse_merge(ids, scores)
+        return IVFKnnResult(ids, scores, scanned, gained)
+
     def close(self):
         """Releases the coarse index."""
         if self.coarse is not None:
             self.coarse.close()
             self.coarse = None
+
+
+class IVFNeighbours:
+    """An :class:`IVFIndex` with the arguments of its ``knn_join``: the handle ``rerank.database_augmentation``,
+    ``rerank.DiffusionGraph`` and ``rerank.ReciprocalEncoding`` take as ``index=`` beside an int8 ``DescriptorIndex``.  The
+    neighbour lists are then approximate (the module docstring says how), and the ``vecs`` of the call must be the index's ``rows``."""
+
+    def __init__(self, index, nprobe, shortlist=None, reverse=True):
+        if not isinstance(index, IVFIndex):
+            raise ValueError("IVFNeighbours: index must be an IVFIndex, got %s" % type(index).__name__)
+        cluster._count(nprobe, "nprobe")
+        if nprobe > index.lists:
+            raise ValueError("nprobe = %d > %d lists" % (nprobe, index.lists))
+        if shortlist is not None:
+            cluster._count(shortlist, "shortlist")
+        if not isinstance(reverse, bool):
+            raise ValueError("reverse must be a bool, got %r" % (reverse,))
+        self.index, self.nprobe, self.shortlist, self.reverse = index, nprobe, shortlist, reverse
+
+    def lists_of(self, vecs, k):
+        """``(ids, scores)`` of ``index.knn_join(k, nprobe, shortlist, reverse)``; ``vecs`` must be the index's rows."""
+        rows = self.index.rows
+        if not isinstance(vecs, torch.Tensor) or vecs.data_ptr() != rows.data_ptr() or tuple(vecs.shape) != tuple(rows.shape) \
+                or vecs.stride() != rows.stride():
+            raise ValueError("IVFNeighbours: vecs must be the rows the index was built on (same storage, shape and strides)")
+        res = self.index.knn_join(k, self.nprobe, shortlist=self.shortlist, reverse=self.reverse)
+        return res.ids, res.scores
 
 
 def _rows_matrix(t, what):

@@ -2135,8 +2135,98 @@ def refine_i8(codes, scales, d, where, qcodes, qscales, ids):
     return out_ids, out_scores
 
 
+# ------------------------------------------------------------------ kNN lists, reverse-edge merge (include/mdx_knn_reverse.h)
+
+KNN_REVERSE_MAX_K = 128           # include/mdx_knn_reverse.h MDX_KNN_REVERSE_MAX_K: two list entries per lane
+
+
+def _knn_reverse_lists(ids, scores, who):
+    """(n, k) of the neighbour lists ``ids`` int64 / ``scores`` fp32 ``[n, k]``, contiguous, on one device."""
+    _kmeans_tensor(ids, torch.int64, who, "ids", 2)
+    n, k = ids.shape
+    _ivf_vector(ids, torch.int64, who, "ids", (n, k), ids.device)
+    _kmeans_tensor(scores, torch.float32, who, "scores", 2)
+    _ivf_vector(scores, torch.float32, who, "scores", (n, k), ids.device)
+    if k > KNN_REVERSE_MAX_K:
+        raise ValueError("%s: k = %d > KNN_REVERSE_MAX_K = %d" % (who, k, KNN_REVERSE_MAX_K))
+    if n * k >= 1 << 31:
+        raise ValueError("%s: n * k = %d must be below 2^31" % (who, n * k))
+    return n, k
+
+
+def knn_reverse_count(ids, scores):
+    """``counts`` int32 ``[n]``: per row the reverse-edge offers that can enter it (``mdx_knn_reverse_count``; the definition is in
+    ``include/mdx_knn_reverse.h``)."""
+    n, k = _knn_reverse_lists(ids, scores, "knn_reverse_count")
+    counts = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_knn_reverse_count(_vp(ids.data_ptr()), _vp(scores.data_ptr()), n, k, _vp(counts.data_ptr()), _stream()),
+              "mdx_knn_reverse_count")
+    return counts
+
+
+def knn_reverse_offsets(counts):
+    """``offsets`` int64 ``[n + 1]`` of the offer segments: 0, then the running sum of ``counts`` (one ``torch.cumsum`` on the
+    device; nothing is read back)."""
+    _kmeans_tensor(counts, torch.int32, "knn_reverse_offsets", "counts", 1)
+    offsets = torch.zeros((counts.shape[0] + 1,), dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=offsets[1:])
+    return offsets
+
+
+def knn_reverse_fill(ids, scores, offsets, capacity=None):
+    """The offer buffer, int64 ``[capacity]`` (an offer is 8 bytes: the score's bits, then the source id as int32), filled along ``offsets`` of :func:`knn_reverse_offsets`
+    (``mdx_knn_reverse_fill``).  ``capacity`` defaults to the bound ``n * k``, which no set of lists exceeds; the order of the offers
+    inside a segment is that of their atomic tickets, and the merge does not depend on it."""
+    who = "knn_reverse_fill"
+    n, k = _knn_reverse_lists(ids, scores, who)
+    capacity = n * k if capacity is None else capacity
+    _ivf_count(capacity, who, "capacity")
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (n + 1,), ids.device)
+    cursor = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    offers = torch.empty((capacity,), dtype=torch.int64, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_knn_reverse_fill(_vp(ids.data_ptr()), _vp(scores.data_ptr()), n, k, _vp(offsets.data_ptr()),
+                                              _vp(cursor.data_ptr()), _vp(offers.data_ptr()), capacity, _stream()), "mdx_knn_reverse_fill")
+    return offers
+
+
+def knn_reverse_apply(ids, scores, offsets, offers):
+    """``(ids int64 [n, k], scores fp32 [n, k], gained int32 [n])``: every row's first ``k`` of its own valid entries and the offers
+    of its segment (``mdx_knn_reverse_merge``)."""
+    who = "knn_reverse_apply"
+    n, k = _knn_reverse_lists(ids, scores, who)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    _ivf_vector(offsets, torch.int64, who, "offsets", (n + 1,), ids.device)
+    _kmeans_tensor(offers, torch.int64, who, "offers", 1)
+    capacity = offers.shape[0]
+    _ivf_vector(offers, torch.int64, who, "offers", (capacity,), ids.device)
+    out_ids = torch.empty((n, k), dtype=torch.int64, device=ids.device)
+    out_scores = torch.empty((n, k), dtype=torch.float32, device=ids.device)
+    gained = torch.empty((n,), dtype=torch.int32, device=ids.device)
+    with _on(ids):
+        check(_lib.lib().mdx_knn_reverse_merge(_vp(ids.data_ptr()), _vp(scores.data_ptr()), n, k, _vp(offsets.data_ptr()),
+                                               _vp(offers.data_ptr()), capacity, _vp(out_ids.data_ptr()), _vp(out_scores.data_ptr()),
+                                               _vp(gained.data_ptr()), _stream()), "mdx_knn_reverse_merge")
+    return out_ids, out_scores, gained
+
+
+def knn_reverse_merge(ids, scores):
+    """The reverse-edge merge of the neighbour lists ``ids`` int64 / ``scores`` fp32 ``[n, k]`` (rows in ``rank_full``'s order, -1
+    padding at the tail, ``k <= KNN_REVERSE_MAX_K``): ``(ids, scores, gained int32 [n])``.  Where row i lists j and j does not list
+    i, ``(i, score)`` is offered to j; every row keeps the first ``k``, by (order key, id), of its own entries and its offers, and
+    ``gained`` counts those that were offers.  The scores are taken to be symmetric (the exact chain is, to the bit); every output score
+    is the bit pattern of an input entry.  :func:`knn_reverse_count`, :func:`knn_reverse_offsets`, :func:`knn_reverse_fill` with the
+    offer buffer at its bound ``n * k``, :func:`knn_reverse_apply`: three launches and a prefix sum, nothing read back."""
+    counts = knn_reverse_count(ids, scores)
+    offsets = knn_reverse_offsets(counts)
+    offers = knn_reverse_fill(ids, scores, offsets)
+    return knn_reverse_apply(ids, scores, offsets, offers)
+
+
 def _csr(id_lists, device):
-    arrays = [np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
+    arrays =[np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)
     if arrays:
         np.cumsum([len(a) for a in arrays], out=offsets[1:])

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from . import _lib, ops, search
+from . import _lib, ivf, ops, search
 from .search import KNN_MEMORY_CAP as DBA_MEMORY_CAP        # bytes of [chunk, N] scores + top-k workspace one DBA chunk may hold
 from .search import _knn_bytes as _dba_bytes
 
@@ -62,7 +62,10 @@ def dba_chunk(n, k, cap=DBA_MEMORY_CAP):
 
 
 def _neighbours(vecs, k, chunk, index):
-    """The exact top-k lists of every row: :func:`search.knn_join` (the exact route, or pruned on an int8 ``index`` of ``vecs``)."""
+    """The top-k lists of every row: exact from :func:`search.knn_join` (the exact route, or pruned on an int8 ``index`` of ``vecs``),
+    or approximate from ``IVFIndex.knn_join`` where ``index`` is an :class:`ivf.IVFNeighbours` whose rows are ``vecs``."""
+    if isinstance(index, ivf.IVFNeighbours):
+        return index.lists_of(vecs, k)
     if index is not None and (not isinstance(index, ops.DescriptorIndex) or index.storage != "i8"):
         raise ValueError("index must be an int8 DescriptorIndex of vecs (storage='i8'), or None for the exact route")
     res = search.knn_join(index, vecs, k, chunk=chunk)
@@ -77,7 +80,9 @@ def database_augmentation(vecs, k, alpha, chunk=None, layout="ND", index=None):
     The neighbour lists are :func:`search.knn_join`'s: the exact fp32 chain, ``chunk`` rows at a time (scores_rowmajor, topk;
     the default chunk keeps each step under ``DBA_MEMORY_CAP`` bytes, :func:`dba_chunk`), or, with ``index`` -- an int8
     ``DescriptorIndex`` of ``vecs`` -- the same lists pruned on the int8 shard; then one ``knn_aggregate``.  The result depends
-    on neither the chunk nor the index.  ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy
+    on neither the chunk nor the index.  (``index`` may also be an ``ivf.IVFNeighbours`` whose rows are ``vecs``: the lists
+    are then ``IVFIndex.knn_join``'s, approximate unless every list is probed -- here, in :class:`DiffusionGraph` and in
+    :class:`ReciprocalEncoding`.)  ``layout="DN"`` accepts the reference's ``[D, N]`` matrix through one transpose copy
     (an ``index`` is of the row-major rows); the result is ``[N, D]`` either way."""
     _check(k, alpha)
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1):

@@ -31,7 +31,11 @@ single-process; not with the re-ranking keys) rescores each query's top-K rows o
 order.  For int8 it prints the certified depth (``ops.rescore_certify``) per query: min / median / max.
 ``neighbours: exact | i8`` (criterion key, default ``exact``; only with ``database_augmentation``, ``diffusion`` or ``k_reciprocal``) chooses how
 their neighbour lists are built: ``i8`` prunes the all-pairs top-k on a temporary int8 index of the rows (``search.knn_join``);
-the lists, and so the results, are the same bits.
+the lists, and so the results, are the same bits.  ``neighbours: {ivf: {lists: L, nprobe: P, storage: f32 | i8, shortlist: S, reverse:
+true | false, iters: .., seed: ..}}`` builds them approximately instead: a temporary ``IVFIndex.train(vecs, L, storage=...)`` and its
+``knn_join`` (``mdir_amd/ivf.py``) -- every row searches its ``P`` best lists and the lists are merged with their reverse edges.
+``lists`` and ``nprobe`` are required; ``storage`` defaults to ``i8``, ``shortlist`` (int8 only) to ``min(4 k_max, 4096)`` over the
+enabled keys, ``reverse`` to true; ``iters`` and ``seed`` go to ``cluster.kmeans``.  Every enabled key needs ``k <= 128``.
 ``k_reciprocal: {k1, k2, lam, truncate}`` (criterion key, every sub-key optional, defaults 20, 6, 0.3, 1000) re-ranks each query's
 ``truncate`` best rows by the Jaccard overlap of k-reciprocal codes (``rerank.k_reciprocal``), after DBA when both are set;
 with ``query_expansion`` the expanded queries' scores are its first stage; not together with ``diffusion`` or ``rescore``;
@@ -47,7 +51,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import ops, rerank
+from . import ivf, ops, rerank
 from .datasets import configdataset, get_data_root, initialize_transforms
 from .evaluate import compute_map_and_print, compute_map_and_print_composite, compute_map_and_print_from_scores
 from .networks import extract_vectors_device
@@ -130,12 +134,16 @@ class CirDatasetAp:
             raise ValueError("k_reciprocal together with diffusion is not supported: choose one")
         # how DBA, the diffusion graph and the k-reciprocal encoding get their neighbour lists: "exact" (fp32 scores of every pair) or "i8" (the same lists,
         # pruned on a temporary int8 index of the rows: search.knn_join)
+        # or {"ivf": {...}}: approximate lists from a temporary inverted file of the rows (IVFIndex.knn_join)
         self.neighbours = params.pop("neighbours", "exact")
-        if self.neighbours not in ("exact", "i8"):
+        depths = [p[key] for p, key in ((self.database_augmentation, "k"), (self.diffusion, "k"), (self.k_reciprocal, "k1")) if p]
+        if isinstance(self.neighbours, dict):
+            self.neighbours = _ivf_neighbours_params(self.neighbours, depths)
+        elif isinstance(self.neighbours, bool) or self.neighbours not in ("exact", "i8"):
             raise ValueError("neighbours: 'exact' or 'i8', got %r" % (self.neighbours,))
-        if self.neighbours != "exact" and not (self.database_augmentation or self.diffusion or self.k_reciprocal):
+        if self.neighbours != "exact" and not depths:
             raise ValueError("neighbours: %s builds the neighbour lists of database_augmentation / diffusion / k_reciprocal; neither is on"
-                             % self.neighbours)
+                             % ("ivf" if isinstance(self.neighbours, dict) else self.neighbours))
         for key in ("database_augmentation", "diffusion"):
             if self.neighbours == "i8" and getattr(self, key) and getattr(self, key)["k"] > ops.KNN_JOIN_MAX_K:
                 raise ValueError("neighbours: i8 keeps at most %d neighbours per row (KNN_JOIN_MAX_K); %s has k=%d"
@@ -302,13 +310,67 @@ def _rerank_params(value, key):
 @contextlib.contextmanager
 def _neighbour_index(vecs, neighbours):
     """The index the neighbour lists are pruned on: a temporary int8 one of ``vecs`` for ``neighbours: i8`` (closed on exit),
-    None for ``exact``."""
+    None for ``exact``; for ``neighbours: {ivf: ...}`` an ``IVFNeighbours`` over a temporary ``IVFIndex.train`` of ``vecs``."""
+    if isinstance(neighbours, dict):
+        p = neighbours["ivf"]
+        index = ivf.IVFIndex.train(vecs, p["lists"], storage=p["storage"], **{key: p[key] for key in ("iters", "seed") if key in p})
+        try:
+            yield ivf.IVFNeighbours(index, p["nprobe"], shortlist=p["shortlist"], reverse=p["reverse"])
+        finally:
+            index.close()
+        return
     index = ops.DescriptorIndex(vecs, "ND", storage="i8") if neighbours == "i8" else None
     try:
         yield index
     finally:
         if index is not None:
             index.close()
+
+
+_IVF_NEIGHBOURS_KEYS = ("lists", "nprobe", "storage", "shortlist", "reverse", "iters", "seed")
+
+
+def _ivf_neighbours_params(value, depths):
+    """``{"ivf": {lists, nprobe, storage, shortlist, reverse[, iters][, seed]}}`` of the ``neighbours`` criterion key with its defaults
+    filled in, validated; ``depths``: the k of every enabled re-ranking key."""
+    if set(value) != {"ivf"} or not isinstance(value["ivf"], dict):
+        raise ValueError("neighbours: 'exact' or 'i8', or the mapping {ivf: {lists, nprobe, ...}}, got %r" % (value,))
+    given = value["ivf"]
+    unknown = set(given) - set(_IVF_NEIGHBOURS_KEYS)
+    if unknown:
+        raise ValueError("neighbours: ivf: unknown keys %s (allowed: %s)" % (sorted(unknown, key=str), ", ".join(_IVF_NEIGHBOURS_KEYS)))
+    for key in ("lists", "nprobe"):
+        if key not in given:
+            raise ValueError("neighbours: ivf: %s is required" % key)
+    out = dict(given)
+    for key in ("lists", "nprobe", "iters"):
+        if key in out and (isinstance(out[key], bool) or not isinstance(out[key], int) or out[key] < 1):
+            raise ValueError("neighbours: ivf: %s must be an integer >= 1, got %r" % (key, out[key]))
+    if "seed" in out and (isinstance(out["seed"], bool) or not isinstance(out["seed"], int) or out["seed"] < 0):
+        raise ValueError("neighbours: ivf: seed must be an integer >= 0, got %r" % (out["seed"],))
+    if out["nprobe"] > out["lists"]:
+        raise ValueError("neighbours: ivf: 1 <= nprobe <= lists is required, got nprobe=%d lists=%d" % (out["nprobe"], out["lists"]))
+    out.setdefault("storage", "i8")
+    if out["storage"] not in ivf.STORAGES:
+        raise ValueError("neighbours: ivf: storage must be 'f32' or 'i8', got %r" % (out["storage"],))
+    out.setdefault("reverse", True)
+    if not isinstance(out["reverse"], bool):
+        raise ValueError("neighbours: ivf: reverse must be true or false, got %r" % (out["reverse"],))
+    deepest = max(depths) if depths else 0
+    if deepest > ops.KNN_REVERSE_MAX_K:
+        raise ValueError("neighbours: ivf keeps at most %d neighbours per row (KNN_REVERSE_MAX_K); an enabled key has k=%d"
+                         % (ops.KNN_REVERSE_MAX_K, deepest))
+    if out["storage"] == "f32":
+        if out.get("shortlist") is not None:
+            raise ValueError("neighbours: ivf: shortlist needs storage: i8 (the fp32 lists are scored exactly)")
+        out["shortlist"] = None
+    else:
+        out.setdefault("shortlist", max(1, min(4 * deepest, ops.RESCORE_MAX_K)))
+        x = out["shortlist"]
+        if isinstance(x, bool) or not isinstance(x, int) or not max(1, deepest) <= x <= ops.RESCORE_MAX_K:
+            raise ValueError("neighbours: ivf: shortlist must be an integer in [k_max, %d] = [%d, %d], got %r"
+                             % (ops.RESCORE_MAX_K, max(1, deepest), ops.RESCORE_MAX_K, x))
+    return {"ivf": out}
 
 
 def _diffusion_params(value):
