@@ -8,8 +8,8 @@
 //   select    one workgroup per query: everything into LDS up to 4096 candidates, a radix select over (order key, id) above that,
 //             then a bitonic sort of the chosen pairs.
 //
-// The sections of the plan, the clamping of the offsets, the checks of the shared sizes and the pad launch of the scan are in
-// mdx_ivf_plan.h, which the int8 scan of the same work items (mdx_lists_i8.hip) includes too.
+// The sections of the plan, the list search and the slot fill of a work item, the checks of the shared sizes and the pad launch of
+// the scan are in mdx_ivf_plan.h, which the int8 scan of the same work items (mdx_lists_i8.hip) includes too.
 #include "mdx_exact.h"
 #include "mdx_ivf_plan.h"
 
@@ -137,13 +137,10 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float *__restrict__
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // everything up to the first barrier is uniform over the workgroup: it leaves as a whole
     if (g >= item[K]) return;                                   // the item does not exist
-    int64_t lo = 0, hi = K;                                     // its list: the last l with item[l] <= g
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (item[mid] <= g) lo = mid; else hi = mid;
-    }
-    const int64_t l = lo, local = g - item[l];
-    const int64_t start = clamp_to(offsets[l], m), size = list_size(offsets, l, m), tiles = (size + TC - 1) / TC;
+    const int64_t l = item_list(item, K, g), local = g - item[l];
+    int64_t start, size;
+    list_extent(offsets, l, m, start, size);
+    const int64_t tiles = (size + TC - 1) / TC;
     if (item[l] < 0 || local < 0 || tiles < 1) return;
     const int64_t t = local % tiles, grp = local / tiles;       // consecutive workgroups share the tile's rows
     const int64_t entries = nq * nprobe;
@@ -157,18 +154,7 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const float *__restrict__
         gid[tid] = id;
         rid[tid] = (tid < in_tile && id >= 0 && id < n) ? id : -1;      // an id outside [0, n) is never dereferenced
     }
-    if (tid < G) {
-        int64_t qi = -1, col = -1;
-        if (tid < ne) {
-            const int64_t e = entry[e0 + tid];
-            if (e >= 0 && e < entries && base[e] >= 0) {
-                qi = e / nprobe;
-                col = base[e] + t * TC;
-            }
-        }
-        qidx[tid] = qi;
-        qcol[tid] = col;
-    }
+    item_slots(tid, t, e0, ne, entry, base, nq, nprobe, qidx, qcol);
     __syncthreads();
     const int64_t d_pad = chain_pad(d), stages = chain_stages(d_pad, KC);
     int64_t my_ids[ROWS_PER_WAVE], my_q[G];
@@ -429,9 +415,7 @@ int mdx_ivf_scan(const float *rows, int64_t n, int64_t d, int64_t ld, const int6
     hipLaunchKernelGGL(ivf_scan_kernel, dim3((unsigned)items), dim3(256), 0, s, rows, n, d, ld, members, m, offsets, K, queries, nq, qlayout,
                        center, nprobe, (const int64_t *)v.base, (const int64_t *)v.first, (const int64_t *)v.item, (const int64_t *)v.entry,
                        cap, vec, cand_scores, cand_ids);
-    const int64_t blocks = ceil_div(cap, 1024);
-    hipLaunchKernelGGL(ivf_pad_kernel, dim3((unsigned)(nq * blocks)), dim3(256), 0, s, (const int64_t *)v.count, cap, blocks, cand_scores,
-                       cand_ids);
+    launch_pad(v, nq, cap, cand_scores, cand_ids, s);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }

@@ -1,9 +1,11 @@
-// The plan of the inverted file (include/mdx_ivf.h) as the kernels that read it see it: its sections, the clamping of the offsets,
-// the checks every call makes of the sizes it shares with the plan, and the second launch of a scan (NaN / -1 beyond a query's
-// count).  Shared by mdx_ivf.hip (the plan itself, the fp32 scan, the selection) and mdx_lists_i8.hip (the int8 scan of the same work
-// items).  Everything sits in an anonymous namespace: each of the two files gets its own copy.
+// The plan of the inverted file (include/mdx_ivf.h) as the kernels that read it see it: its sections, the list of a work item and
+// the slots of its entries, the checks every call makes of the sizes it shares with the plan, and the second launch of a scan
+// (NaN / -1 beyond a query's count).  Shared by mdx_ivf.hip (the plan itself, the fp32 scan, the selection), mdx_lists_i8.hip (the
+// int8 scan of the same work items) and mdx_lists_pq.hip (the query-major ADC scan).  Everything sits in an anonymous namespace: each
+// file gets its own copy.
 #pragma once
 #include "mdx_common.h"
+#include "mdx_lists_clamp.h"
 
 namespace mdx {
 namespace {
@@ -41,13 +43,32 @@ static inline Plan carve(const void *plan, int64_t nq, int64_t nprobe, int64_t K
     return v;
 }
 
-__device__ __forceinline__ int64_t clamp_to(int64_t o, int64_t hi) { return o < 0 ? 0 : o > hi ? hi : o; }
-
-// the members list l has after clamping its offsets to [0, m]
-__device__ __forceinline__ int64_t list_size(const int64_t *__restrict__ offsets, int64_t l, int64_t m)
+// the list of work item g of a list-major scan: the last l with item[l] <= g
+__device__ __forceinline__ int64_t item_list(const int64_t *__restrict__ item, int64_t K, int64_t g)
 {
-    const int64_t lo = clamp_to(offsets[l], m), hi = clamp_to(offsets[l + 1], m);
-    return hi > lo ? hi - lo : 0;
+    int64_t lo = 0, hi = K;
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (item[mid] <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// threads 0 .. G - 1: the query of entry e0 + tid (-1 without one) and the column of tile t's first member in its candidate row
+__device__ __forceinline__ void item_slots(int tid, int64_t t, int64_t e0, int ne, const int64_t *__restrict__ entry,
+                                           const int64_t *__restrict__ base, int64_t nq, int64_t nprobe, int64_t *qidx, int64_t *qcol)
+{
+    if (tid >= G) return;
+    int64_t qi = -1, col = -1;
+    if (tid < ne) {
+        const int64_t e = entry[e0 + tid];
+        if (e >= 0 && e < nq * nprobe && base[e] >= 0) {
+            qi = e / nprobe;
+            col = base[e] + t * TC;
+        }
+    }
+    qidx[tid] = qi;
+    qcol[tid] = col;
 }
 
 // the columns at or beyond a query's count: NaN / -1.  One workgroup per (query, 1024 columns)
@@ -61,6 +82,14 @@ __global__ __launch_bounds__(256) void ivf_pad_kernel(const int64_t *__restrict_
         cand_scores[q * cap + c] = __builtin_nanf("");
         cand_ids[q * cap + c] = -1;
     }
+}
+
+// the second launch of every scan
+static inline void launch_pad(const Plan &v, int64_t nq, int64_t cap, float *cand_scores, int64_t *cand_ids, hipStream_t s)
+{
+    const int64_t blocks = ceil_div(cap, 1024);
+    hipLaunchKernelGGL(ivf_pad_kernel, dim3((unsigned)(nq * blocks)), dim3(256), 0, s, (const int64_t *)v.count, cap, blocks, cand_scores,
+                       cand_ids);
 }
 
 // the sizes every call shares, and the plan

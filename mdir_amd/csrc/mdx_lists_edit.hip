@@ -8,7 +8,7 @@
 //             of a wave ascend with its reads.
 #include <initializer_list>
 
-#include "mdx_common.h"
+#include "mdx_lists_clamp.h"
 
 namespace mdx {
 namespace {
@@ -24,17 +24,6 @@ template <int W> struct Piece;
 template <> struct Piece<16> { typedef int type __attribute__((ext_vector_type(4))); };
 template <> struct Piece<4> { typedef uint32_t type; };
 template <> struct Piece<1> { typedef uint8_t type; };
-
-// as clamp_to and list_size of mdx_ivf_plan.h
-__device__ __forceinline__ int64_t clamp_to(int64_t o, int64_t hi) { return o < 0 ? 0 : o > hi ? hi : o; }
-
-// where list l starts after clamping its offsets to [0, m], and the rows it has
-__device__ __forceinline__ void list_extent(const int64_t *__restrict__ offsets, int64_t l, int64_t m, int64_t &start, int64_t &size)
-{
-    const int64_t lo = clamp_to(offsets[l], m), hi = clamp_to(offsets[l + 1], m);
-    start = lo;
-    size = hi > lo ? hi - lo : 0;
-}
 
 // ------------------------------------------------------------------------------------------------------------------ merge
 

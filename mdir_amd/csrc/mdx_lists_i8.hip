@@ -143,15 +143,12 @@ __global__ __launch_bounds__(256) void lists_scan_kernel(const int8_t *__restric
     __shared__ int64_t qidx[G], qcol[G];        // the entry's query, -1 without one; the column of the tile's first member
     const int64_t g = blockIdx.x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // everything up to the first barrier is uniform over the workgroup: it leaves as a whole (as ivf_scan_kernel)
+    // everything up to the first barrier is uniform over the workgroup: it leaves as a whole
     if (g >= item[K]) return;                                   // the item does not exist
-    int64_t lo = 0, hi = K;                                     // its list: the last l with item[l] <= g
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (item[mid] <= g) lo = mid; else hi = mid;
-    }
-    const int64_t l = lo, local = g - item[l];
-    const int64_t start = clamp_to(offsets[l], m), size = list_size(offsets, l, m), tiles = (size + TC - 1) / TC;
+    const int64_t l = item_list(item, K, g), local = g - item[l];
+    int64_t start, size;
+    list_extent(offsets, l, m, start, size);
+    const int64_t tiles = (size + TC - 1) / TC;
     if (item[l] < 0 || local < 0 || tiles < 1) return;
     const int64_t t = local % tiles, grp = local / tiles;       // consecutive workgroups share the tile's codes
     const int64_t entries = nq * nprobe;
@@ -165,18 +162,7 @@ __global__ __launch_bounds__(256) void lists_scan_kernel(const int8_t *__restric
         gid[tid] = tid < in_tile ? members[pos0 + tid] : -1;
         msc[tid] = tid < in_tile ? scales[pos0 + tid] : __builtin_nanf("");
     }
-    if (tid < G) {
-        int64_t qi = -1, col = -1;
-        if (tid < ne) {
-            const int64_t e = entry[e0 + tid];
-            if (e >= 0 && e < entries && base[e] >= 0) {
-                qi = e / nprobe;
-                col = base[e] + t * TC;
-            }
-        }
-        qidx[tid] = qi;
-        qcol[tid] = col;
-    }
+    item_slots(tid, t, e0, ne, entry, base, nq, nprobe, qidx, qcol);
     // rows G .. 15 of the B operand are zero for good: one 16-byte piece per thread and row
     for (int r = G + wave; r < 16; r += 4) *(i32x4 *)(qs + r * QLD + 16 * lane) = (i32x4){0, 0, 0, 0};
     __syncthreads();
@@ -307,9 +293,7 @@ int mdx_lists_i8_scan(const int8_t *codes, const float *scales, int64_t m, int64
     hipLaunchKernelGGL(lists_scan_kernel, dim3((unsigned)items), dim3(256), 0, s, codes, scales, m, d, members, offsets, K, qcodes, qscales, nq,
                        nprobe, (const int64_t *)v.base, (const int64_t *)v.first, (const int64_t *)v.item, (const int64_t *)v.entry, cap, qvec,
                        cand_scores, cand_ids);
-    const int64_t blocks = ceil_div(cap, 1024);
-    hipLaunchKernelGGL(ivf_pad_kernel, dim3((unsigned)(nq * blocks)), dim3(256), 0, s, (const int64_t *)v.count, cap, blocks, cand_scores,
-                       cand_ids);
+    launch_pad(v, nq, cap, cand_scores, cand_ids, s);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }

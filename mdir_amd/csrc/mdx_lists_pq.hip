@@ -126,7 +126,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void lists_pq_scan_kernel(const uint8
         const int64_t e = q * nprobe + p;
         const int64_t l = probes[e], b = base[e];
         if (l < 0 || l >= K || b < 0) continue;                   // a probe outside the lists, or one the plan marks invalid
-        const int64_t start = clamp_to(offsets[l], m), size = list_size(offsets, l, m);
+        int64_t start, size;
+        list_extent(offsets, l, m, start, size);
         const float c0 = coarse[e];
         for (int64_t i = lane; i < size; i += WAVE) {
             const int64_t col = b + i;
@@ -195,9 +196,7 @@ int mdx_lists_pq_scan(const uint8_t *codes, int64_t m, int64_t M, int64_t ldc, c
     hipLaunchKernelGGL(lists_pq_scan_kernel, dim3((unsigned)(nq * splits)), dim3(SCAN_THREADS), (size_t)(M * CW * 4), s, codes, m, (int)M, ldc,
                        width, members, n, offsets, K, lut, lvec, coarse, probes, nq, nprobe, splits, (const int64_t *)v.base, cap, cand_scores,
                        cand_ids);
-    const int64_t blocks = ceil_div(cap, 1024);
-    hipLaunchKernelGGL(ivf_pad_kernel, dim3((unsigned)(nq * blocks)), dim3(256), 0, s, (const int64_t *)v.count, cap, blocks, cand_scores,
-                       cand_ids);
+    launch_pad(v, nq, cap, cand_scores, cand_ids, s);
     MDX_LAUNCH_CHECK();
     return MDX_OK;
 }

@@ -118,25 +118,22 @@ def item_bound(tiles_np, tiles_all, nq):
     return max(1, (shared + (g - 1) * min(tiles_all, shared)) // g)
 
 
-class IVFIndex:
-    """The inverted file of ``rows`` over ``centroids`` -- the module docstring states the contract."""
+class InvertedLists:
+    """What :class:`IVFIndex` and ``ivfpq.IVFPQIndex`` share: the partition and what follows from its list sizes, the checks of a
+    search's queries, and the two ends of a search step, between which each storage puts its scan.  ``n`` is the id bound and
+    ``size`` the number of positions, which only an index that removes rows tells apart."""
 
-    storage, codes, scales, bounds = "f32", None, None, None
+    _home = "rows"             # what the queries must share a device with, in the words of the messages
 
-    def __init__(self, rows, centroids, labels=None, chunk=None, storage="f32"):
-        if storage not in STORAGES:
-            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
+    def _build(self, rows, centroids, labels, chunk):
+        """Checks the arguments, makes the partition (``order``, ``offsets``, ``sizes`` and what ``_set_sizes`` derives, after the one
+        read-back) and the coarse index; ``(labels, sizes)``: the labels, given or assigned, and the list sizes on the device."""
         _rows_matrix(rows, "rows")
         cluster._matrix(centroids, "centroids")
         if centroids.shape[1] != rows.shape[1]:
             raise ValueError("centroids are [K, %d] and rows [N, %d]: the dimensions differ" % (centroids.shape[1], rows.shape[1]))
         n, k = rows.shape[0], centroids.shape[0]
-        if labels is not None:
-            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
-                raise ValueError("labels must be an int64 [%d] tensor, got %s" % (
-                    n, "%s %s" % (labels.dtype, tuple(labels.shape)) if isinstance(labels, torch.Tensor) else type(labels).__name__))
-        elif not rows.is_contiguous():
-            raise ValueError("rows must be contiguous to be assigned (labels=None)")
+        _labels_fit(labels, rows, "rows")
         if chunk is not None:
             cluster._count(chunk, "chunk")
         cluster._on_device(rows, "rows")
@@ -144,56 +141,31 @@ class IVFIndex:
         if centroids.device != rows.device:
             raise ValueError("centroids are on %s and rows on %s" % (centroids.device, rows.device))
         if labels is not None:
-            cluster._on_device(labels, "labels")
-            if labels.device != rows.device:
-                raise ValueError("labels are on %s and rows on %s" % (labels.device, rows.device))
-            low, high = int(labels.min()), int(labels.max())
-            if low < 0 or high >= k:
-                raise ValueError("labels must lie in [0, %d), got %d .. %d" % (k, low, high))
+            _labels_in_range(labels, k, rows.device, "rows")
         else:
             labels = cluster.assign(centroids, rows, chunk)[0]
-        self.rows, self.centroids, self.labels, self.fit = rows, centroids, labels, None
-        self.n, self.d, self.lists = n, rows.shape[1], k
-        self.order, self.offsets, self.sizes = cluster._members(labels, k)
-        # the one read-back: list sizes, and what follows from them for every nprobe
-        self.host_sizes = self.sizes.cpu().tolist()
-        by_size = sorted(self.host_sizes, reverse=True)
+        self.rows, self.centroids, self.fit = rows, centroids, None
+        self.n, self.size, self.d, self.lists = n, n, rows.shape[1], k
+        self.order, self.offsets, sizes = cluster._members(labels, k)
+        self._set_sizes(sizes.cpu().tolist())                                   # the one read-back
+        self.coarse = ops.DescriptorIndex(centroids, "ND")
+        return labels, sizes
+
+    def _set_sizes(self, host_sizes):
+        """The list sizes on the host and what follows from them for every nprobe: the candidates and the tiles of the largest lists."""
+        self.host_sizes = host_sizes
         self._capacity, self._tiles = [0], [0]
-        for s in by_size:
+        for s in sorted(host_sizes, reverse=True):
             self._capacity.append(self._capacity[-1] + s)
             self._tiles.append(self._tiles[-1] + -(-s // ops.IVF_TILE))
-        self.storage = storage
-        if storage == "i8":
-            self.codes, self.scales = ops.lists_i8_encode(rows, self.order)
-            self.bounds = ops.lists_i8_bounds(self.codes, self.scales, self.d)
-        self.coarse = ops.DescriptorIndex(centroids, "ND")
-
-    @classmethod
-    def train(cls, rows, lists, storage="f32", **kmeans_kwargs):
-        """The index of ``cluster.kmeans(rows, lists, **kmeans_kwargs)``; the fit stays reachable as ``.fit``."""
-        if storage not in STORAGES:
-            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
-        fit = cluster.kmeans(rows, lists, **kmeans_kwargs)
-        index = cls(rows, fit.centroids, fit.labels, storage=storage)
-        index.fit = fit
-        return index
 
     def capacity(self, nprobe):
         """The most candidates a query can have with ``nprobe`` probes: the sum of the ``nprobe`` largest list sizes (at least 1)."""
         return max(1, self._capacity[nprobe])
 
     def items(self, nq, nprobe):
-        """The workgroups ``search`` launches for the scan of ``nq`` queries: :func:`item_bound` of this index."""
+        """The workgroups ``search`` launches for a list-major scan of ``nq`` queries: :func:`item_bound` of this index."""
         return item_bound(self._tiles[nprobe], self._tiles[-1], nq)
-
-    def query_chunk(self, nprobe, shortlist=None):
-        """Queries per step of ``search``: as many as keep the candidate block under ``CANDIDATE_MEMORY_CAP`` bytes (at least one).  On an
-        int8 index a query also holds its centred row, codes and scale (``5 d + 4`` bytes) and, with a shortlist of ``S``, the int8
-        selection, the rescored pairs and the unsorted scores (``28 S``) and its depth and bound (8)."""
-        per_query = 12 * self.capacity(nprobe)
-        if self.storage == "i8":
-            per_query += 5 * self.d + 4 + (0 if shortlist is None else 28 * shortlist + 8)
-        return max(1, CANDIDATE_MEMORY_CAP // per_query)
 
     def _check_search(self, queries, k, nprobe, qlayout, center):
         if self.coarse is None:
@@ -218,10 +190,81 @@ class IVFIndex:
                                    or not center.is_contiguous()):
             raise ValueError("center must be a contiguous fp32 tensor of %d elements" % self.d)
         cluster._on_device(queries, "queries")
-        if queries.device != self.rows.device:
-            raise ValueError("queries are on %s and rows on %s" % (queries.device, self.rows.device))
-        if center is not None and center.device != self.rows.device:
-            raise ValueError("center is on %s and rows on %s" % (center.device, self.rows.device))
+        if queries.device != self.device:
+            raise ValueError("queries are on %s and %s on %s" % (queries.device, self._home, self.device))
+        if center is not None and center.device != self.device:
+            raise ValueError("center is on %s and %s on %s" % (center.device, self._home, self.device))
+
+    def _chunked(self, step, kind, chunk, queries, qlayout, *args):
+        """``step`` on the queries ``chunk`` at a time; the parts of every field back to back (a field that is None stays None)."""
+        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
+        if nq <= chunk:
+            return step(queries, qlayout, *args)
+        parts = []
+        for q0 in range(0, nq, chunk):
+            block = queries[q0:q0 + chunk] if qlayout == "ND" else queries[:, q0:q0 + chunk].contiguous()
+            parts.append(step(block, qlayout, *args))
+        return kind(*(None if parts[0][i] is None else torch.cat([p[i] for p in parts]) for i in range(len(parts[0]))))
+
+    def _probe(self, queries, qlayout, center, nprobe):
+        """The front half of a search step: ``(probes, their coarse values, plan, cap)``.  The plan counts positions (``size``)."""
+        probes, coarse = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
+        cap = self.capacity(nprobe)
+        return probes, coarse, ops.ivf_plan(probes, self.offsets, self.size, cap), cap
+
+    def _select(self, cand_scores, cand_ids, plan, nprobe, k):
+        """The tail of a search step: ``(ids, scores)`` of the first ``k`` candidates, and ``scanned``, the plan's count of them."""
+        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k)
+        return ids, scores, ops.ivf_plan_views(plan, ids.shape[0], nprobe, self.lists)["count"].clone()
+
+    # The -1 ids that pad a shortlist go to its second stage as the id n (the id bound): never dereferenced, scored NaN, and behind
+    # every candidate in the order of the rescored row, where the fp32 search has its padding.  They come back as -1.
+    def _pad_in(self, ids):
+        return torch.where(ids < 0, self.n, ids)
+
+    def _pad_out(self, ids):
+        return torch.where(ids >= self.n, -1, ids)
+
+    def close(self):
+        """Releases the coarse index."""
+        if self.coarse is not None:
+            self.coarse.close()
+            self.coarse = None
+
+
+class IVFIndex(InvertedLists):
+    """The inverted file of ``rows`` over ``centroids`` -- the module docstring states the contract."""
+
+    storage, codes, scales, bounds = "f32", None, None, None
+    device = property(lambda self: self.rows.device)
+
+    def __init__(self, rows, centroids, labels=None, chunk=None, storage="f32"):
+        if storage not in STORAGES:
+            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
+        self.labels, self.sizes = self._build(rows, centroids, labels, chunk)
+        self.storage = storage
+        if storage == "i8":
+            self.codes, self.scales = ops.lists_i8_encode(rows, self.order)
+            self.bounds = ops.lists_i8_bounds(self.codes, self.scales, self.d)
+
+    @classmethod
+    def train(cls, rows, lists, storage="f32", **kmeans_kwargs):
+        """The index of ``cluster.kmeans(rows, lists, **kmeans_kwargs)``; the fit stays reachable as ``.fit``."""
+        if storage not in STORAGES:
+            raise ValueError("storage %r (\"f32\" or \"i8\")" % (storage,))
+        fit = cluster.kmeans(rows, lists, **kmeans_kwargs)
+        index = cls(rows, fit.centroids, fit.labels, storage=storage)
+        index.fit = fit
+        return index
+
+    def query_chunk(self, nprobe, shortlist=None):
+        """Queries per step of ``search``: as many as keep the candidate block under ``CANDIDATE_MEMORY_CAP`` bytes (at least one).  On an
+        int8 index a query also holds its centred row, codes and scale (``5 d + 4`` bytes) and, with a shortlist of ``S``, the int8
+        selection, the rescored pairs and the unsorted scores (``28 S``) and its depth and bound (8)."""
+        per_query = 12 * self.capacity(nprobe)
+        if self.storage == "i8":
+            per_query += 5 * self.d + 4 + (0 if shortlist is None else 28 * shortlist + 8)
+        return max(1, CANDIDATE_MEMORY_CAP // per_query)
 
     def _check_stages(self, k, shortlist, exact):
         cluster._count(k, "k")
@@ -256,46 +299,26 @@ class IVFIndex:
             res.scores.index_copy_(0, fallback, sure.scores)
         return res._replace(fallback=fallback)
 
-    def _chunked(self, step, kind, chunk, queries, qlayout, *args):
-        """``step`` on the queries ``chunk`` at a time; the parts of every field back to back (a field that is None stays None)."""
-        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
-        if nq <= chunk:
-            return step(queries, qlayout, *args)
-        parts = []
-        for q0 in range(0, nq, chunk):
-            block = queries[q0:q0 + chunk] if qlayout == "ND" else queries[:, q0:q0 + chunk].contiguous()
-            parts.append(step(block, qlayout, *args))
-        return kind(*(None if parts[0][i] is None else torch.cat([p[i] for p in parts]) for i in range(len(parts[0]))))
-
     def _search(self, queries, qlayout, k, nprobe, center):
-        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
-        probes, _ = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
-        cap = self.capacity(nprobe)
-        plan = ops.ivf_plan(probes, self.offsets, self.n, cap)
-        cand_scores, cand_ids = ops.ivf_scan(self.rows, self.order, self.offsets, queries, plan, nprobe, cap, self.items(nq, nprobe),
-                                             qlayout, None if center is None else center.reshape(-1))
-        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k)
-        scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
+        probes, _, plan, cap = self._probe(queries, qlayout, center, nprobe)
+        cand_scores, cand_ids = ops.ivf_scan(self.rows, self.order, self.offsets, queries, plan, nprobe, cap,
+                                             self.items(probes.shape[0], nprobe), qlayout, None if center is None else center.reshape(-1))
+        ids, scores, scanned = self._select(cand_scores, cand_ids, plan, nprobe, k)
         return IVFResult(ids, scores, probes, scanned)
 
     def _search_i8(self, queries, qlayout, k, nprobe, center, shortlist):
-        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
         center = None if center is None else center.reshape(-1)
-        probes, _ = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
-        cap = self.capacity(nprobe)
-        plan = ops.ivf_plan(probes, self.offsets, self.n, cap)
+        probes, _, plan, cap = self._probe(queries, qlayout, center, nprobe)
         qcodes, qscales = ops.quantize_i8(ops.center_rows(queries, qlayout, center))
         cand_scores, cand_ids = ops.lists_i8_scan(self.codes, self.scales, self.d, self.order, self.offsets, qcodes, qscales, plan, nprobe,
-                                                  cap, self.items(nq, nprobe))
-        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k if shortlist is None else shortlist)
-        scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
+                                                  cap, self.items(probes.shape[0], nprobe))
+        ids, scores, scanned = self._select(cand_scores, cand_ids, plan, nprobe, k if shortlist is None else shortlist)
         none = torch.empty(0, dtype=torch.int64, device=self.rows.device)
         if shortlist is None:
             return IVFRescored(ids, scores, probes, scanned, None, none)
         del cand_scores, cand_ids
-        # the padding of a shortlist as the id n: not dereferenced, NaN, and behind every candidate in the order of the rescored row
-        sure_ids, sure = ops.rescore(self.rows, queries, torch.where(ids < 0, self.n, ids), qlayout, center)
-        sure_ids = torch.where(sure_ids >= self.n, -1, sure_ids)
+        sure_ids, sure = ops.rescore(self.rows, queries, self._pad_in(ids), qlayout, center)
+        sure_ids = self._pad_out(sure_ids)
         depth, _ = ops.rescore_certify(sure, scores[:, shortlist - 1], queries, self.bounds, max(self.n, shortlist), qlayout, center)
         certified = torch.where(scanned <= shortlist, shortlist, depth.to(torch.int64))
         return IVFRescored(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned, certified, none)
@@ -340,13 +363,6 @@ class IVFIndex:
         ids, scores, gained = ops.knn_reverse_merge(ids, scores)
         return IVFKnnResult(ids, scores, scanned, gained)
 
-    def close(self):
-        """Releases the coarse index."""
-        if self.coarse is not None:
-            self.coarse.close()
-            self.coarse = None
-
-
 class IVFNeighbours:
     """An :class:`IVFIndex` with the arguments of its ``knn_join``: the handle ``rerank.database_augmentation``,
     ``rerank.DiffusionGraph`` and ``rerank.ReciprocalEncoding`` take as ``index=`` beside an int8 ``DescriptorIndex``.  The
@@ -372,6 +388,26 @@ class IVFNeighbours:
             raise ValueError("IVFNeighbours: vecs must be the rows the index was built on (same storage, shape and strides)")
         res = self.index.knn_join(k, self.nprobe, shortlist=self.shortlist, reverse=self.reverse)
         return res.ids, res.scores
+
+
+def _labels_fit(labels, vectors, what):
+    """Explicit labels are an int64 tensor with one entry per vector; without them the vectors (named ``what``) must be contiguous."""
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (vectors.shape[0],):
+            raise ValueError("labels must be an int64 [%d] tensor, got %s" % (
+                vectors.shape[0], "%s %s" % (labels.dtype, tuple(labels.shape)) if isinstance(labels, torch.Tensor) else type(labels).__name__))
+    elif not vectors.is_contiguous():
+        raise ValueError("%s must be contiguous to be assigned (labels=None)" % what)
+
+
+def _labels_in_range(labels, lists, device, home):
+    """Explicit labels lie on ``device`` (where ``home`` is, in the words of the message) and in ``[0, lists)`` -- one read-back."""
+    cluster._on_device(labels, "labels")
+    if labels.device != device:
+        raise ValueError("labels are on %s and %s on %s" % (labels.device, home, device))
+    low, high = int(labels.min()), int(labels.max())
+    if low < 0 or high >= lists:
+        raise ValueError("labels must lie in [0, %d), got %d .. %d" % (lists, low, high))
 
 
 def _rows_matrix(t, what):

@@ -7,8 +7,9 @@ distance computation (ADC): the coarse score of the list plus ``M`` entries of a
 ``tests/pq_restatement.py`` states the search in numpy.
 
 ``IVFPQIndex(rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, refine=None, **pq_train_kwargs)``
-    ``rows``, ``centroids``, ``labels`` and ``chunk`` as for ``ivf.IVFIndex``, which builds the partition: ``order``, ``offsets``, the
-    list sizes on the host, ``capacity(nprobe)`` and ``coarse``, the fp32 index of the centroids, are its.  ``D % m == 0`` and
+    ``rows``, ``centroids``, ``labels`` and ``chunk`` as for ``ivf.IVFIndex``; the base the two share, ``ivf.InvertedLists``, builds the
+    partition: ``order``, ``offsets``, the list sizes on the host, ``capacity(nprobe)`` and ``coarse``, the fp32 index of the
+    centroids, are its.  ``D % m == 0`` and
     ``1 <= m <= ops.PQ_MAX_M``.  The residuals ``r = row - centroids[label]`` (one fp32 subtraction per element) are taken in list
     order, ``chunk`` rows at a time (default ``pq.CHUNK``).  ``codebook=None`` runs ``pq.train(residuals, m, **pq_train_kwargs)`` on all
     of them (a transient fp32 ``[N, D]`` block; ``N >= 256``); a :data:`pq.Codebook` is taken as it is.  ``codes`` uint8 ``[N, m]`` is
@@ -130,11 +131,12 @@ def _check_refine(refine, d):
         raise ValueError("refine=\"i8\": D = %d > %d" % (d, ops.LISTS_I8_MAX_D))
 
 
-class IVFPQIndex:
+class IVFPQIndex(ivf.InvertedLists):
     """The inverted file of the product-quantised residuals of ``rows`` over ``centroids`` -- the module docstring states the
     contract."""
 
     refine = None              # "i8": refine_codes, refine_scales and where are kept
+    _home = "the index"
 
     def __init__(self, rows, centroids, labels=None, m=64, codebook=None, keep_rows=True, chunk=None, refine=None, **pq_train_kwargs):
         ivf._rows_matrix(rows, "rows")
@@ -151,17 +153,14 @@ class IVFPQIndex:
                     m_have, _pq.CODEWORDS, dsub_have, m, rows.shape[1], m, _pq.CODEWORDS, dsub))
         elif rows.shape[0] < _pq.CODEWORDS:
             raise ValueError("N = %d rows: pq.train needs at least %d" % (rows.shape[0], _pq.CODEWORDS))
-        partition = ivf.IVFIndex(rows, centroids, labels, chunk)       # every other check, the lists, the capacities, the coarse index
-        self.n, self.d, self.lists, self.m = partition.n, partition.d, partition.lists, m
-        self.order, self.offsets, self.host_sizes = partition.order, partition.offsets, partition.host_sizes
-        self._capacity, self.coarse, self.fit = partition._capacity, partition.coarse, None
-        self.device, self.centroids, self.size = rows.device, centroids, partition.n
+        labels, _ = self._build(rows, centroids, labels, chunk)         # every other check, the lists, the capacities, the coarse index
+        self.m, self.device = m, rows.device
         try:
             step = min(self.n, chunk or _pq.CHUNK)
             if codebook is None:
                 residuals = torch.empty((self.n, self.d), dtype=torch.float32, device=self.device)
                 for p0 in range(0, self.n, step):
-                    residuals[p0:p0 + step] = self._residuals(rows, centroids, partition.labels, p0, p0 + step)
+                    residuals[p0:p0 + step] = self._residuals(rows, centroids, labels, p0, p0 + step)
                 codebook = _pq.train(residuals, m, chunk=chunk, **pq_train_kwargs)
                 self.codes = _pq.encode(codebook, residuals, chunk)
                 del residuals
@@ -170,7 +169,7 @@ class IVFPQIndex:
                     raise ValueError("the codebook is on %s and rows on %s" % (words.device, self.device))
                 self.codes = torch.empty((self.n, m), dtype=torch.uint8, device=self.device)
                 for p0 in range(0, self.n, step):
-                    self.codes[p0:p0 + step] = _pq.encode(codebook, self._residuals(rows, centroids, partition.labels, p0, p0 + step))
+                    self.codes[p0:p0 + step] = _pq.encode(codebook, self._residuals(rows, centroids, labels, p0, p0 + step))
             if refine is not None:
                 self.refine = refine
                 self.refine_codes, self.refine_scales = ops.lists_i8_encode(rows, self.order)
@@ -216,10 +215,6 @@ class IVFPQIndex:
             held += 4 * self.rows.shape[0] * (self.rows.stride(0) if self.rows.shape[0] > 1 else self.rows.shape[1])
         return held
 
-    def capacity(self, nprobe):
-        """The most candidates a query can have with ``nprobe`` probes: the sum of the ``nprobe`` largest list sizes (at least 1)."""
-        return max(1, self._capacity[nprobe])
-
     def query_chunk(self, nprobe, shortlist=None):
         """Queries per step of ``search``: as many as keep their candidate rows (12 bytes a column), their tables (``m`` KiB each) and,
         with a shortlist of ``S``, the selection and the rescored pairs (``28 S``) under ``ivf.CANDIDATE_MEMORY_CAP`` (at least one).  On a
@@ -251,70 +246,38 @@ class IVFPQIndex:
                     "a shortlist" if self.refine is None else "rescore = %d of the refined shortlist" % rescore))
         elif rescore is not None:
             raise ValueError("rescore = %r needs a shortlist" % (rescore,))
-        if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32 or queries.dim() != 2 or queries.numel() < 1:
-            raise ValueError("queries must be a non-empty fp32 2-d tensor, got %s" % (
-                "%s %s" % (queries.dtype, tuple(queries.shape)) if isinstance(queries, torch.Tensor) else type(queries).__name__))
-        if qlayout not in ("ND", "DN"):
-            raise ValueError("qlayout %r (\"ND\" or \"DN\")" % (qlayout,))
-        dq = queries.shape[1] if qlayout == "ND" else queries.shape[0]
-        if dq != self.d:
-            raise ValueError("queries have dimension %d and the rows %d" % (dq, self.d))
-        if not queries.is_contiguous():
-            raise ValueError("queries must be contiguous")
-        cluster._count(nprobe, "nprobe")
-        if nprobe > self.lists:
-            raise ValueError("nprobe = %d > %d lists" % (nprobe, self.lists))
-        if center is not None and (not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.numel() != self.d
-                                   or not center.is_contiguous()):
-            raise ValueError("center must be a contiguous fp32 tensor of %d elements" % self.d)
-        cluster._on_device(queries, "queries")
-        if queries.device != self.device:
-            raise ValueError("queries are on %s and the index on %s" % (queries.device, self.device))
-        if center is not None and center.device != self.device:
-            raise ValueError("center is on %s and the index on %s" % (center.device, self.device))
+        super()._check_search(queries, k, nprobe, qlayout, center)
 
     def search(self, queries, k, nprobe, qlayout="ND", center=None, shortlist=None, rescore=None):
         """:data:`IVFPQResult` of the ``k`` best rows of every query among the members of its ``nprobe`` best lists, by ADC score or,
         with a shortlist, by the exact score of the ADC shortlist -- on a ``refine="i8"`` index by its int8 score, and with ``rescore=R``
         by the exact score of the ``R`` best of those -- the module docstring has the contract."""
         self._check_search(queries, k, nprobe, qlayout, center, shortlist, rescore)
-        return ivf.IVFIndex._chunked(self, self._search, IVFPQResult, self.query_chunk(nprobe, shortlist), queries, qlayout, k, nprobe,
-                                     center, shortlist, rescore)
+        return self._chunked(self._search, IVFPQResult, self.query_chunk(nprobe, shortlist), queries, qlayout, k, nprobe, center, shortlist,
+                             rescore)
 
     def _search(self, queries, qlayout, k, nprobe, center, shortlist, rescore=None):
-        nq = queries.shape[0] if qlayout == "ND" else queries.shape[1]
         center = None if center is None else center.reshape(-1)
-        probes, coarse = ops.topk(self.coarse.scores(queries, qlayout, center=center), nprobe)
-        cap = self.capacity(nprobe)
-        plan = ops.ivf_plan(probes, self.offsets, self.size, cap)    # the positions; self.n below is the id bound
+        probes, coarse, plan, cap = self._probe(queries, qlayout, center, nprobe)     # the plan counts positions; self.n is the id bound
         lut = ops.pq_lut(self.codebook.codewords, queries, qlayout, center)
         cand_scores, cand_ids = ops.lists_pq_scan(self.codes, self.order, self.n, self.offsets, lut, coarse, probes, plan, cap)
-        ids, scores = ops.ivf_select(cand_scores, cand_ids, plan, nprobe, self.lists, k if shortlist is None else shortlist)
-        scanned = ops.ivf_plan_views(plan, nq, nprobe, self.lists)["count"].clone()
+        ids, scores, scanned = self._select(cand_scores, cand_ids, plan, nprobe, k if shortlist is None else shortlist)
         if shortlist is None:
             return IVFPQResult(ids, scores, probes, scanned)
         del cand_scores, cand_ids, lut
-        # the padding of a shortlist as the id n: not dereferenced, NaN, and behind every candidate in the order of the rescored row
-        ids = torch.where(ids < 0, self.n, ids)
+        ids = self._pad_in(ids)
         if self.refine is not None:
             qcodes, qscales = ops.quantize_i8(ops.center_rows(queries, qlayout, center))
             ids, fine = ops.refine_i8(self.refine_codes, self.refine_scales, self.d, self.where, qcodes, qscales, ids)
             if rescore is None:
-                ids = torch.where(ids >= self.n, -1, ids)
+                ids = self._pad_out(ids)
                 return IVFPQResult(ids[:, :k].contiguous(), fine[:, :k].contiguous(), probes, scanned)
             ids = ids[:, :rescore].contiguous()
         sure_ids, sure = ops.rescore(self.rows, queries, ids, qlayout, center)
-        sure_ids = torch.where(sure_ids >= self.n, -1, sure_ids)
+        sure_ids = self._pad_out(sure_ids)
         return IVFPQResult(sure_ids[:, :k].contiguous(), sure[:, :k].contiguous(), probes, scanned)
 
     # -------------------------------------------------------------------------------------------- after the build
-
-    @staticmethod
-    def _capacities(host_sizes):
-        capacity = [0]
-        for s in sorted(host_sizes, reverse=True):
-            capacity.append(capacity[-1] + s)
-        return capacity
 
     def _check_edit(self, what):
         if self.coarse is None:
@@ -331,12 +294,7 @@ class IVFPQIndex:
         b = batch.shape[0]
         if batch.shape[1] != self.d:
             raise ValueError("batch is [B, %d] and the index has D = %d" % (batch.shape[1], self.d))
-        if labels is not None:
-            if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or tuple(labels.shape) != (b,):
-                raise ValueError("labels must be an int64 [%d] tensor, got %s" % (
-                    b, "%s %s" % (labels.dtype, tuple(labels.shape)) if isinstance(labels, torch.Tensor) else type(labels).__name__))
-        elif not batch.is_contiguous():
-            raise ValueError("batch must be contiguous to be assigned (labels=None)")
+        ivf._labels_fit(labels, batch, "batch")
         if chunk is not None:
             cluster._count(chunk, "chunk")
         if self.n + b >= 1 << 31:
@@ -345,12 +303,7 @@ class IVFPQIndex:
         if batch.device != self.device:
             raise ValueError("batch is on %s and the index on %s" % (batch.device, self.device))
         if labels is not None:
-            cluster._on_device(labels, "labels")
-            if labels.device != self.device:
-                raise ValueError("labels are on %s and the index on %s" % (labels.device, self.device))
-            low, high = int(labels.min()), int(labels.max())
-            if low < 0 or high >= self.lists:
-                raise ValueError("labels must lie in [0, %d), got %d .. %d" % (self.lists, low, high))
+            ivf._labels_in_range(labels, self.lists, self.device, self._home)
         else:
             labels = cluster.assign(self.centroids, batch, chunk)[0]
         members, offsets, _ = cluster._members(labels, self.lists)
@@ -367,7 +320,7 @@ class IVFPQIndex:
         host_sizes = (merged[2][1:] - merged[2][:-1]).cpu().tolist()             # the one read-back
         ids = torch.arange(self.n, self.n + b, dtype=torch.int64, device=self.device)
         self.codes, self.order, self.offsets = merged
-        self.host_sizes, self._capacity = host_sizes, self._capacities(host_sizes)
+        self._set_sizes(host_sizes)
         self.n, self.size = self.n + b, self.size + b
         if self.refine is not None:
             self.refine_codes, self.refine_scales = fine[0].view(torch.int8), fine[1].view(torch.float32).view(self.size)
@@ -398,7 +351,8 @@ class IVFPQIndex:
                 fine = [ops.lists_compact(mine.view(torch.uint8).view(self.size, -1), self.order, self.offsets, kept, total)[0]
                         for mine in (self.refine_codes, self.refine_scales)]
             self.codes, self.order, self.offsets = ops.lists_compact(self.codes, self.order, self.offsets, kept, total)
-            self.host_sizes, self._capacity, self.size = host_sizes, self._capacities(host_sizes), total
+            self._set_sizes(host_sizes)
+            self.size = total
             if self.refine is not None:
                 self.refine_codes, self.refine_scales = fine[0].view(torch.int8), fine[1].view(torch.float32).view(total)
                 self.where = self._where()
@@ -468,15 +422,8 @@ class IVFPQIndex:
         if index.refine is not None:
             index.where = index._where()
         index.codebook = _pq.Codebook(codewords, [], 0)
-        index.host_sizes = (offsets[1:] - offsets[:-1]).cpu().tolist()             # the one read-back
-        index._capacity = cls._capacities(index.host_sizes)
+        index._set_sizes((offsets[1:] - offsets[:-1]).cpu().tolist())              # the one read-back
         index.coarse = None
         index.attach_rows(rows)
         index.coarse = ops.DescriptorIndex(centroids, "ND")
         return index
-
-    def close(self):
-        """Releases the coarse index."""
-        if self.coarse is not None:
-            self.coarse.close()
-            self.coarse = None

@@ -1740,6 +1740,21 @@ def _ivf_plan_arg(plan, who, nq, nprobe, k, device):
     return _vp(plan.data_ptr())
 
 
+def _ivf_lists(who, members, offsets, m, device):
+    """The lists of a scan, checked: ``members`` int64 ``[m]`` (``m=None``: as many as there are) and ``offsets`` int64 ``[K + 1]``,
+    contiguous on ``device``; ``(members pointer, offsets pointer, m, K)``."""
+    _kmeans_tensor(members, torch.int64, who, "members", 1)
+    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
+    m, k = members.shape[0] if m is None else m, offsets.shape[0] - 1
+    return (_ivf_vector(members, torch.int64, who, "members", (m,), device),
+            _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), device), m, k)
+
+
+def _ivf_candidates(nq, cap, device):
+    """The outputs of a scan, uninitialised: ``(cand_scores fp32 [nq, cap], cand_ids int64 [nq, cap])``."""
+    return torch.empty((nq, cap), dtype=torch.float32, device=device), torch.empty((nq, cap), dtype=torch.int64, device=device)
+
+
 def ivf_plan_views(plan, nq, nprobe, k):
     """The sections of a plan (include/mdx_ivf.h) as int64 views of it: ``{"base": [nq, nprobe], "count": [nq], "first": [k + 1],
     "item": [k + 1], "entry": [nq * nprobe]}``.  Of ``entry`` only the first ``first[k]`` are defined, and inside a list in no
@@ -1795,21 +1810,16 @@ def ivf_scan(rows, members, offsets, queries, plan, nprobe, cap, items, qlayout=
         raise ValueError("%s: query dimension %d != rows dimension %d" % (who, dq, d))
     if not queries.is_contiguous() or queries.device != rows.device:
         raise ValueError("%s: queries must be contiguous on %s" % (who, rows.device))
-    _kmeans_tensor(members, torch.int64, who, "members", 1)
-    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
-    m, k = members.shape[0], offsets.shape[0] - 1
-    _ivf_vector(members, torch.int64, who, "members", (m,), rows.device)
-    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), rows.device)
+    mp, op, m, k = _ivf_lists(who, members, offsets, None, rows.device)
     for x, what in ((nprobe, "nprobe"), (cap, "cap"), (items, "items")):
         _ivf_count(x, who, what)
     cp = None
     if center is not None:
         cp = _ivf_vector(center, torch.float32, who, "center", (d,), rows.device)
     pp = _ivf_plan_arg(plan, who, nq, nprobe, k, rows.device)
-    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=rows.device)
-    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=rows.device)
+    cand_scores, cand_ids = _ivf_candidates(nq, cap, rows.device)
     with _on(rows):
-        check(_lib.lib().mdx_ivf_scan(rp, n, d, ld, _vp(members.data_ptr()), m, _vp(offsets.data_ptr()), k, _vp(queries.data_ptr()), nq, lay,
+        check(_lib.lib().mdx_ivf_scan(rp, n, d, ld, mp, m, op, k, _vp(queries.data_ptr()), nq, lay,
                                       cp, nprobe, pp, plan.numel(), cap, items, _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()),
                                       _stream()), "mdx_ivf_scan")
     return cand_scores, cand_ids
@@ -1906,18 +1916,13 @@ def lists_i8_scan(codes, scales, d, members, offsets, qcodes, qscales, plan, npr
     _ivf_vector(qcodes, torch.int8, who, "qcodes", (nq, d), codes.device)
     _kmeans_tensor(qscales, torch.float32, who, "qscales", 1)
     _ivf_vector(qscales, torch.float32, who, "qscales", (nq,), codes.device)
-    _kmeans_tensor(members, torch.int64, who, "members", 1)
-    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
-    k = offsets.shape[0] - 1
-    _ivf_vector(members, torch.int64, who, "members", (m,), codes.device)
-    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), codes.device)
+    mp, op, m, k = _ivf_lists(who, members, offsets, m, codes.device)
     for x, what in ((nprobe, "nprobe"), (cap, "cap"), (items, "items")):
         _ivf_count(x, who, what)
     pp = _ivf_plan_arg(plan, who, nq, nprobe, k, codes.device)
-    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=codes.device)
-    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=codes.device)
+    cand_scores, cand_ids = _ivf_candidates(nq, cap, codes.device)
     with _on(codes):
-        check(_lib.lib().mdx_lists_i8_scan(cp, sp, m, d, _vp(members.data_ptr()), _vp(offsets.data_ptr()), k, _vp(qcodes.data_ptr()),
+        check(_lib.lib().mdx_lists_i8_scan(cp, sp, m, d, mp, op, k, _vp(qcodes.data_ptr()),
                                            _vp(qscales.data_ptr()), nq, nprobe, pp, plan.numel(), cap, items,
                                            _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()), _stream()), "mdx_lists_i8_scan")
     return cand_scores, cand_ids
@@ -1987,18 +1992,13 @@ def lists_pq_scan(codes, members, n, offsets, lut, coarse, probes, plan, cap):
     _ivf_vector(probes, torch.int64, who, "probes", (nq, nprobe), codes.device)
     _kmeans_tensor(coarse, torch.float32, who, "coarse", 2)
     _ivf_vector(coarse, torch.float32, who, "coarse", (nq, nprobe), codes.device)
-    _kmeans_tensor(members, torch.int64, who, "members", 1)
-    _kmeans_tensor(offsets, torch.int64, who, "offsets", 1)
-    k = offsets.shape[0] - 1
-    _ivf_vector(members, torch.int64, who, "members", (m,), codes.device)
-    _ivf_vector(offsets, torch.int64, who, "offsets", (k + 1,), codes.device)
+    mp, op, m, k = _ivf_lists(who, members, offsets, m, codes.device)
     for x, what in ((n, "n"), (cap, "cap")):
         _ivf_count(x, who, what)
     pp = _ivf_plan_arg(plan, who, nq, nprobe, k, codes.device)
-    cand_scores = torch.empty((nq, cap), dtype=torch.float32, device=codes.device)
-    cand_ids = torch.empty((nq, cap), dtype=torch.int64, device=codes.device)
+    cand_scores, cand_ids = _ivf_candidates(nq, cap, codes.device)
     with _on(codes):
-        check(_lib.lib().mdx_lists_pq_scan(_vp(codes.data_ptr()), m, sub, ldc, _vp(members.data_ptr()), n, _vp(offsets.data_ptr()), k,
+        check(_lib.lib().mdx_lists_pq_scan(_vp(codes.data_ptr()), m, sub, ldc, mp, n, op, k,
                                            _vp(lut.data_ptr()), _vp(coarse.data_ptr()), _vp(probes.data_ptr()), nq, nprobe, pp, plan.numel(),
                                            cap, _vp(cand_scores.data_ptr()), _vp(cand_ids.data_ptr()), _stream()), "mdx_lists_pq_scan")
     return cand_scores, cand_ids

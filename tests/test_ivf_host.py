@@ -351,3 +351,23 @@ def test_index_refusals_need_no_gpu():
     assert index.query_chunk(1) == ivf.CANDIDATE_MEMORY_CAP // (12 * 130)
     index._capacity = [0, 0]
     assert index.capacity(1) == 1
+
+
+def test_both_indices_derive_the_same_capacities_from_one_set_sizes():
+    """``_set_sizes`` is the base's: a bare ``IVFIndex`` and a bare ``IVFPQIndex`` given the same list sizes agree on ``_capacity``,
+    ``capacity(p)`` is the sum of the ``p`` largest sizes and ``items(nq, p)`` the ``item_bound`` of the tiles of those lists."""
+    from mdir_amd import ivf, ivfpq, ops
+    sizes = (0, 1, 63, 64, 65, 130)
+    plain, coded = ivf.IVFIndex.__new__(ivf.IVFIndex), ivfpq.IVFPQIndex.__new__(ivfpq.IVFPQIndex)
+    assert type(plain)._set_sizes is type(coded)._set_sizes
+    for index in (plain, coded):
+        index._set_sizes(list(sizes))
+        assert index.host_sizes == list(sizes)
+    assert plain._capacity == coded._capacity and plain._tiles == coded._tiles
+    by_size = sorted(sizes, reverse=True)
+    tiles = [-(-s // ops.IVF_TILE) for s in by_size]
+    for p in range(1, 7):
+        for index in (plain, coded):
+            assert index.capacity(p) == sum(by_size[:p])
+            for nq in (1, 17, 100):
+                assert index.items(nq, p) == ivf.item_bound(sum(tiles[:p]), sum(tiles), nq)
