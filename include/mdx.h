@@ -1053,6 +1053,18 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * Additions: MDX_ABI_VERSION stays. */
 #include "mdx_knn_reverse.h"
 
+/* ------------------------------- U-Net epilogue */
+
+/* The generators in front of the embedding network (mdir_amd/unet.py; a SequentialNetwork checkpoint = U-Net + trunk) run at the full
+ * image size, and around their library convolutions they have what mdx_bn_act removed from the trunk -- full-tensor passes for the conv
+ * bias, the batch-norm and the activation -- plus one torch.cat per level.  mdx_bn_act_into is mdx_bn_act's first three lines with
+ * ReLU or LeakyReLU, written into a channel slice of a wider tensor: each half of a skip connection is produced in place in the concat
+ * buffer.  The whole contract -- the value to the bit, the slice, the overlap rule, the launch shape, the refusals -- is stated in
+ * mdx_unet.h, beside this file, with the prototype; its name is in _lib.UNET_EXPORTS, for the reason given above for mdx_knn_join.h,
+ * and its census is tests/test_unet_host.py (exported, bound, and covered by tests/test_gpu_unet_memcontract.py).
+ * An addition: MDX_ABI_VERSION stays. */
+#include "mdx_unet.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -7,7 +7,8 @@
 model)``.  ``SingleNetwork`` / ``CirNetwork`` keep the reference's constructor,
 ``overlay_params`` and checkpoint layout (``{"type","frozen","network_params":{"model",
 "runtime"},"model_state"}``, network.py:142-170).  Training-side methods
-(parameters, freeze, graphs) and ``SequentialNetwork`` are out of scope.
+(parameters, freeze, graphs) are out of scope.  ``SequentialNetwork`` is the inference slice of ``network.py:204-345``: a U-Net
+generator (``unet.py``) in front of the embedding network, one checkpoint.
 """
 import copy
 from collections import namedtuple
@@ -15,6 +16,7 @@ from collections import namedtuple
 import torch
 
 from .networks import init_network
+from .unet import MODEL_LABELS as UNET_LABELS
 from .wrapper import initialize_wrappers
 
 
@@ -33,7 +35,7 @@ def init_cirnet(**params):
     return net
 
 
-MODEL_LABELS = {"cirnet": init_cirnet}
+MODEL_LABELS = {"cirnet": init_cirnet, **UNET_LABELS}
 
 
 def initialize_model(params):
@@ -110,7 +112,120 @@ class CirNetwork(SingleNetwork):
         super().__init__(model, network_params, device, frozen)
 
 
-NETWORKS = {"SingleNetwork": SingleNetwork, "CirNetwork": CirNetwork}
+class SequentialNetwork:
+    """Member networks run one after the other: ``sequence = [first, last]``, the first a generator whose output the last
+    embeds.  The pre- and post-processing chain of the whole is the LAST network's (its own is emptied), the data section the
+    FIRST's; ``model`` is the last network's, which is what the wrappers ask for pooling exponent and descriptor width."""
+    TRAIN, EVAL = "train", "eval"
+    NetworkParams = namedtuple("NetworkParams", ["runtime"])
+
+    def __init__(self, networks, sequence, device, frozen):
+        assert len(networks) == len(sequence) == 2, (len(networks), sequence)      # as the reference: pairs only
+        self.sequence = sequence
+        self.networks = networks
+        first, last = networks[sequence[0]], networks[sequence[1]]
+        # every refusal before anything is taken from a member: a failed construction leaves the members as they were
+        for net in networks.values():
+            if net.network_params.runtime.get("precision", "f32") != "f32":
+                raise NotImplementedError("precision: %s on a SequentialNetwork: the generators run in fp32 only"
+                                          % net.network_params.runtime["precision"])
+        if first.meta["in_channels"] != 3:
+            raise NotImplementedError("a first network with in_channels=%s: the multi-channel input transforms (tospace, "
+                                      "add_clahe_fromrgb, replace_histogram) are out of scope" % first.meta["in_channels"])
+        assert first.meta["out_channels"] == last.meta["in_channels"], (first.meta, last.meta)
+        self.frozen = frozen
+        self.model = last.model
+        self.stage = None
+        self.wrappers = last.wrappers
+        last.wrappers = {x: initialize_wrappers("", device) for x in ["train", "eval"]}
+        self.network_params = self.NetworkParams({"wrappers": last.network_params.runtime.get("wrappers", ""),
+                                                  "data": first.network_params.runtime.get("data", {})})
+        self.meta = {"in_channels": first.meta["in_channels"], "out_channels": last.meta["out_channels"]}
+        if frozen:
+            self.eval()
+
+    @property
+    def supports_batches(self):
+        """A batch goes through the members' models directly (``forward``); a member with a chain of its own is called as a
+        network, one image at a time."""
+        return all(not self.networks[net].wrappers[self.stage or self.EVAL].wrappers for net in self.sequence)
+
+    def __call__(self, image):
+        return self.wrappers[self.stage](image, self.forward, self.model)
+
+    def __getitem__(self, key):
+        return self.networks[key]
+
+    def forward(self, image):
+        for name in self.sequence:
+            net = self.networks[name]
+            # an empty chain is `model(image.to(device))`; calling the model keeps a batch's [D,B] as the outer chain expects it
+            image = net(image) if net.wrappers[net.stage].wrappers else net.model(image)
+        return image
+
+    def eval(self):
+        for net in self.sequence:
+            self.networks[net].eval()
+        self.stage = self.EVAL
+        return self
+
+    def overlay_params(self, new_params, device):
+        if not new_params:
+            return self
+        diff = set(self.sequence) - set(new_params.keys())
+        assert not diff, diff
+        # a last member without an overlay of its own keeps the chain of the pair, which lives here (its own was emptied)
+        acc = {}
+        for net in self.sequence:
+            acc[net] = self.networks[net].overlay_params(new_params[net], device)
+            if acc[net] is self.networks[net] and net == self.sequence[-1]:
+                acc[net] = copy.copy(acc[net])
+                acc[net].wrappers = self.wrappers
+        return self.__class__(acc, self.sequence, device=device, frozen=True)
+
+    def state_dict(self):
+        hierarchy, state = {}, {}
+        for net in self.sequence:
+            netstate = self.networks[net].state_dict()
+            netstate[net] = netstate.pop("net")
+            overlap = set(state.keys()).intersection(netstate.keys())
+            assert not overlap, overlap
+            hierarchy[net] = [x for x in netstate if x != net]
+            state.update(netstate)
+        state["net"] = {"type": self.__class__.__name__, "frozen": self.frozen, "sequence": self.sequence,
+                        "network_hierarchy": hierarchy}
+        return state
+
+    @classmethod
+    def initialize_from_state(cls, state_dict, device, params, runtime):
+        state_dict = dict(state_dict)
+        checkpoint = state_dict.pop("net")
+        assert checkpoint["type"] == cls.__name__, checkpoint["type"]
+        if not {"sequence", "network_hierarchy"} <= checkpoint.keys():
+            raise NotImplementedError("not a complete SequentialNetwork checkpoint: %s lacks 'sequence' / 'network_hierarchy' "
+                                      "(a SequentialNetwork = U-Net generator + embedding network, DESIGN.md section 7)"
+                                      % sorted(checkpoint.keys()))
+        assert checkpoint.keys() == {"type", "frozen", "sequence", "network_hierarchy"}, checkpoint.keys()
+        assert set(checkpoint["sequence"]) == checkpoint["network_hierarchy"].keys()
+        runtime = dict(runtime) if runtime else {}
+        if runtime.pop("precision", "f32") != "f32":                  # f32 is what a sequence runs in: nothing to pass on
+            raise NotImplementedError("precision: f16 on a SequentialNetwork: the generators run in fp32 only")
+        propagated = {net: None for net in checkpoint["sequence"]}
+        if "wrappers" in runtime:
+            propagated[checkpoint["sequence"][-1]] = {"wrappers": runtime.pop("wrappers")}
+        if "data" in runtime:
+            first = checkpoint["sequence"][0]
+            propagated[first] = {**(propagated[first] or {}), "data": runtime.pop("data")}
+        assert not runtime, runtime
+        acc = {}
+        for net in checkpoint["network_hierarchy"]:
+            netstate = {x: state_dict[x] for x in checkpoint["network_hierarchy"][net]}
+            netstate["net"] = state_dict[net]
+            acc[net] = NETWORKS[state_dict[net]["type"]].initialize_from_state(netstate, device, None, propagated[net])
+        return cls(acc, checkpoint["sequence"], device=device, frozen=checkpoint["frozen"])
+
+
+NETWORKS = {"SingleNetwork": SingleNetwork, "CirNetwork": CirNetwork, "SequentialNetwork": SequentialNetwork}
 
 
 def load_checkpoint(path):
@@ -125,10 +240,11 @@ def initialize_network(params, device, state=None, runtime=None):
     assert state is not None, "only checkpoint-backed networks are supported on the eval path"
     kind = state["net"]["type"]
     if kind not in NETWORKS:
-        raise NotImplementedError("network type %r is outside the MI355X hot path (%s are supported; "
-                                  "SequentialNetwork = U-Net generator + embedding network, DESIGN.md section 7)"
+        raise NotImplementedError("network type %r is outside the MI355X hot path (%s are supported, DESIGN.md section 7)"
                                   % (kind, sorted(NETWORKS)))
     cls = NETWORKS[kind]
+    if cls is SequentialNetwork:                        # its member networks are further top-level entries of the checkpoint
+        return cls.initialize_from_state(state, device, params, runtime)
     return cls.initialize_from_state({"net": state["net"]}, device, params, runtime)
 
 

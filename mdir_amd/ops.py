@@ -442,6 +442,48 @@ def bn_act_(x, running_mean, running_var, weight=None, bias=None, eps=1e-5, resi
     return x
 
 
+ACT_NONE, ACT_RELU, ACT_LEAKY = _lib.MDX_ACT_NONE, _lib.MDX_ACT_RELU, _lib.MDX_ACT_LEAKY
+
+
+def bn_act_into(x, out_view, running_mean=None, running_var=None, weight=None, bias=None, eps=1e-5, act=ACT_RELU, slope=0.0):
+    """Inference batch-norm / conv bias and an activation of a convolution output ``x [N,C,H,W]`` in one pass, written into
+    ``out_view`` (``mdx_bn_act_into``, include/mdx_unet.h); returns ``out_view``.  ``out_view`` is ``x`` itself (in place) or a
+    channel slice ``buf[:, c0:c0 + C]`` of a contiguous ``[N, Ctot, H, W]`` tensor: same shape as ``x``, contiguous planes one
+    after the other, any distance between images.  ``act``: ``ACT_NONE``, ``ACT_RELU``, ``ACT_LEAKY`` (with ``slope``).  Unlike
+    ``bn_act_`` nothing is added after the ``fmaf``, so a -0 stays -0."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("bn_act_into expects a contiguous fp32 [N,C,H,W] CUDA/ROCm tensor (no CPU fallback)")
+    n, c, h, w = x.shape
+    if not (isinstance(out_view, torch.Tensor) and out_view.shape == x.shape and out_view.dtype == x.dtype
+            and out_view.device == x.device):
+        raise ValueError("out_view must be an fp32 tensor shaped like x on %s" % (x.device,))
+    if act not in (ACT_NONE, ACT_RELU, ACT_LEAKY):
+        raise ValueError("act=%r (ACT_NONE, ACT_RELU or ACT_LEAKY)" % (act,))
+    ptrs = []
+    for name, t in (("running_mean", running_mean), ("running_var", running_var), ("weight", weight), ("bias", bias)):
+        if t is None:
+            ptrs.append(None)
+            continue
+        if t.numel() != c or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous():
+            raise ValueError("%s must be %d contiguous fp32 values on %s" % (name, c, x.device))
+        ptrs.append(t.data_ptr())
+    if (ptrs[0] is None) != (ptrs[1] is None):
+        raise ValueError("running_mean and running_var must both be given or both be None")
+    if x.numel() == 0:
+        return out_view
+    hw = h * w
+    sn, sc, sh, sw = out_view.stride()
+    # a channel slice: the planes of one image follow one another as in x (a size-1 dimension's stride is arbitrary in torch)
+    if (w > 1 and sw != 1) or (h > 1 and sh != w) or (c > 1 and sc != hw) or (n > 1 and sn < c * hw):
+        raise ValueError("out_view is not a channel slice of a contiguous [N,Ctot,H,W] tensor: strides %s for shape %s"
+                         % ((sn, sc, sh, sw), tuple(x.shape)))
+    stride = sn if n > 1 else c * hw
+    with _on(x):
+        check(_lib.lib().mdx_bn_act_into(x.data_ptr(), out_view.data_ptr(), n, c, hw, stride, ptrs[0], ptrs[1], ptrs[2], ptrs[3],
+                                         float(eps), int(act), float(slope), _stream()), "mdx_bn_act_into")
+    return out_view
+
+
 def conv1x1_transpose_weights(weight):
     """``[Cout, Cin(,1,1)]`` convolution weights -> the ``[Cin, Cout]`` copy ``conv1x1_bn_act`` reads (made once)."""
     w = weight.reshape(weight.shape[0], -1)
