@@ -1065,6 +1065,17 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * An addition: MDX_ABI_VERSION stays. */
 #include "mdx_unet.h"
 
+/* ------------------------------- top-K lists, overlap */
+
+/* How much of one set of top-K lists another holds: per query and depth, the ids of the head of a[q] that occur in the head of b[q] --
+ * the count behind recall@depth of an approximate search (mdir_amd/ivf.py, mdir_amd/ivfpq.py, search.search) against the exact top-K,
+ * for up to 8 depths in one launch (search.recall_at; the `search` criterion key of mdir_amd/score.py prints it).  One workgroup per
+ * query, row b in an open-addressing table in LDS, integers only.  The whole contract -- the definition, padding and large ids, the
+ * launch shape, the refusals -- is stated in mdx_overlap.h, beside this file, with the prototype; its name is in _lib.OVERLAP_EXPORTS,
+ * for the reason given above for mdx_knn_join.h, and its census is tests/test_overlap_host.py (exported, bound, and covered by
+ * tests/test_gpu_overlap_memcontract.py).  An addition: MDX_ABI_VERSION stays. */
+#include "mdx_overlap.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

@@ -10,6 +10,10 @@ come either from a materialised ranking (``ranks[:, q]``, numpy or torch, any
 device -- the reference call style) or straight from the scores through the HIP
 counting kernel (``positions_from_scores`` -> ``mdx_rank_of``), which yields the
 same numbers without sorting a million-row database.
+
+Not in the reference: ``compute_map_topk`` / ``compute_map_and_print_topk`` evaluate top-K lists -- the first K entries of every
+query's ranking, which is all an inverted file or a shortlist search returns -- as truncated rankings; with K >= N they are the
+functions above, bit for bit.
 """
 import numpy as np
 
@@ -392,3 +396,166 @@ def compute_map_and_print_composite(dataset, scores, head, gnd, kappas=[1, 5, 10
     ``rank_full(scores)`` with its first K columns replaced by ``head``)."""
     positions = _positions_of_rows(scores.shape[1], gnd, lambda lists: positions_composite(scores, head, lists))
     return _evaluate(dataset, gnd, kappas, lambda g, k: positions.map(g, k), positions)
+
+
+# ------------------------------------------------------------------------------------------------ top-K lists (truncated rankings)
+
+class _WithStats(tuple):
+    """A result tuple that also carries ``.stats`` -- what a truncated evaluation knows beside the reference's outputs."""
+    stats = None
+
+    def __new__(cls, items, stats):
+        self = super().__new__(cls, items)
+        self.stats = stats
+        return self
+
+
+def _head_array(heads):
+    if torch is not None and isinstance(heads, torch.Tensor):
+        if heads.dtype != torch.int64 or heads.dim() != 2:
+            raise ValueError("heads: an int64 [Q, K] tensor or array, got %s %s" % (heads.dtype, tuple(heads.shape)))
+        return heads if heads.is_cuda else heads.numpy()
+    heads = np.asarray(heads)
+    if heads.dtype != np.int64 or heads.ndim != 2:
+        raise ValueError("heads: an int64 [Q, K] tensor or array, got %s %s" % (heads.dtype, heads.shape))
+    return heads
+
+
+def positions_in_heads(heads, id_lists):
+    """Positions of ids inside top-K lists ``heads`` int64 ``[Q, K]`` (row q = the first K of query q's ranking, -1 = padding): one
+    int64 array per query aligned with ``id_lists[q]`` (sorted, unique, non-negative), -1 where the id is not in the head.  A device
+    tensor goes through ``ops.rank_positions`` (one pass for all queries), a host array through ``np.isin`` row by row."""
+    if _is_device_tensor(heads):
+        from . import ops
+        pos, off = ops.rank_positions(heads if heads.is_contiguous() else heads.contiguous(), id_lists)
+        pos = pos.cpu().numpy()
+        return [pos[off[q]:off[q + 1]] for q in range(len(id_lists))]
+    out = []
+    for q, ids in enumerate(id_lists):
+        found = np.full(len(ids), -1, dtype=np.int64)
+        if len(ids):
+            at = np.nonzero(np.isin(heads[q], ids))[0]
+            found[np.searchsorted(ids, heads[q][at])] = at
+        out.append(found)
+    return out
+
+
+def _head_positions(heads, gnd, n):
+    """(:class:`_Positions` of every labelled id in the heads, valid entries per query)."""
+    heads = _head_array(heads)
+    if len(gnd) != heads.shape[0]:
+        raise ValueError("heads has %d rows for %d queries" % (heads.shape[0], len(gnd)))
+    valid = (heads >= 0).sum(1)
+    valid = valid.cpu().numpy() if _is_device_tensor(heads) else np.asarray(valid)
+    return _positions_of_rows(n, gnd, lambda lists: positions_in_heads(heads, lists)), valid.astype(np.int64)
+
+
+def _map_of_heads(positions, valid, gnd, n, kappas):
+    """The arithmetic of :func:`compute_map_topk` on fetched head positions: ``(map, aps, pr, prs)`` with ``.stats``."""
+    oks, junks, nok = labelled_lists(gnd, n)
+    nq = len(gnd)
+    aps = np.zeros(nq)
+    prs = np.zeros((nq, len(kappas)))
+    pr, seen = np.zeros(len(kappas)), np.zeros(len(kappas), dtype=np.int64)
+    found, rows, depth = (np.zeros(nq, dtype=np.int64) for _ in range(3))
+    total, nempty = 0.0, 0
+    for q in range(nq):
+        rows[q] = len(oks[q])
+        if nok[q] == 0:
+            aps[q] = float("nan")
+            prs[q, :] = float("nan")
+            depth[q] = valid[q]
+            nempty += 1
+            continue
+        pos, junk = positions.of(q, oks[q]), positions.of(q, junks[q])
+        if len(junk):
+            pos = pos - np.searchsorted(junk, pos, side="left")      # evaluate.py:85-100: the junk before a found positive is in the head
+        found[q], depth[q] = len(pos), valid[q] - len(junk)
+        ap = compute_ap(pos, nok[q])
+        aps[q] = ap
+        total += ap
+        if len(kappas):
+            pos1 = pos + 1
+            complete = rows[q] > 0 and found[q] == rows[q]
+            for j, kappa in enumerate(kappas):
+                if complete:
+                    kq = min(int(pos1.max()), kappa)                 # evaluate.py:102-106, unchanged
+                elif kappa <= depth[q]:
+                    kq = kappa                                       # the last positive lies at or beyond depth >= kappa
+                else:
+                    prs[q, j] = float("nan")                         # the head does not determine min(max(pos) + 1, kappa)
+                    continue
+                prs[q, j] = (pos1 <= kq).sum() / kq
+                pr[j] = pr[j] + prs[q, j]
+                seen[j] += 1
+    if len(kappas) and nq - nempty and (seen == nq - nempty).all():
+        pr = pr / (nq - nempty)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pr = pr / seen                                           # nanmean: the undetermined queries are skipped
+    return _WithStats((total / (nq - nempty), aps, pr, prs), {"found": found, "rows": rows, "depth": depth})
+
+
+def compute_map_topk(heads, gnd, n, kappas=[], _positions=None):
+    """mAP of top-K lists: :func:`compute_map` for rankings of which only the first K entries are known.
+
+    ``heads``: int64 ``[Q, K]``, a device tensor or a numpy array; row q holds the first K entries of query q's ranking, best
+    first.  Every non-negative id of a row is distinct; -1 is padding and stands at the tail only.  ``n``: the database rows.
+    ``gnd[q]``: ``ok`` ids, optional ``junk`` ids, read as :func:`labelled_lists` reads them: duplicates collapse, ids outside
+    ``[0, n)`` occupy no position, the normaliser stays ``len(ok)`` as given.  Device heads are searched by
+    ``ops.rank_positions``, host heads with ``np.isin`` row by row.
+
+    AP.  ``compute_ap(adjusted positions of the positives found in the head, len(ok))``: the junk shift counts the junk found in
+    the head before each positive, and junk ranked before a found positive lies inside the head, so every term is, bit for bit,
+    that positive's term of the full ranking's AP and the head's AP is the left-to-right partial sum of the full AP.  Positives
+    that are not in the head contribute nothing; a query with none of them found has AP 0.0 (nothing raises).  The normaliser is
+    the reference's, ``len(ok)``, not ``min(len(ok), K)``.
+
+    P@kappa.  The reference computes ``kq = min(max(pos) + 1, kappa)`` over ALL positives.  Let ``m_q`` = the valid entries (id
+    >= 0) of row q minus the junk found in it.  If every positive that is a database row was found (and there is one), the
+    reference's formula is used unchanged.  Otherwise the last positive sits at an adjusted position ``>= m_q``: for ``kappa <=
+    m_q`` that gives ``kq = kappa`` and the value ``(hits within kappa) / kappa`` -- what any full ranking that starts with this
+    head gives; for ``kappa > m_q`` the head does not determine the value and it is NaN.  The mean over the queries skips the NaN
+    entries as ``np.nanmean`` does.  Queries with ``len(ok) == 0`` are NaN and excluded, as in :func:`compute_map`.
+
+    Returns ``(map, aps, pr, prs)``; the tuple's ``.stats`` holds int64 arrays per query: ``found`` (positives found), ``rows``
+    (positives that are database rows) and ``depth`` (``m_q``).
+
+    Contract: with ``K >= n`` and full rankings as heads, this returns what :func:`compute_map` returns for ``heads.T``, bit for bit.
+    """
+    if _positions is None:
+        _positions = _head_positions(heads, gnd, n)
+    return _map_of_heads(_positions[0], _positions[1], gnd, n, list(kappas))
+
+
+def compute_map_and_print_topk(dataset, heads, gnd, n, kappas=[1, 5, 10]):
+    """:func:`compute_map_and_print` for top-K lists (:func:`compute_map_topk` states the arithmetic and the P@kappa rule): the
+    protocol dispatch, the printed lines and the returned ``(averages, per_query)`` dicts are the reference's, nothing added; one
+    more ``>>`` line prints the label recall, ``found / rows`` averaged over the queries that have a positive among the database
+    rows.  The result's ``.stats`` holds ``found`` / ``rows`` / ``depth`` of :func:`compute_map_topk` -- for the revisited
+    protocol one such dict per level (``easy``, ``medium``, ``hard``).  The heads are searched once for all levels.
+
+    Contract: with ``K >= n`` and full rankings as heads, this returns what :func:`compute_map_and_print` returns, bit for bit."""
+    positions = _head_positions(heads, gnd, n)
+    stats = []
+
+    def one_map(g, k):
+        res = compute_map_topk(heads, g, n, k, _positions=positions)
+        stats.append(res.stats)
+        return res
+
+    out = _evaluate(dataset, gnd, kappas, one_map)
+    if out is None:
+        return None
+    stats = stats[0] if len(stats) == 1 else {level: s for (level, _, _), s in zip(_LEVELS, stats)}
+    recalls = [label_recall(s) for s in (stats.values() if "found" not in stats else [stats])]
+    r = lambda v: np.around(v * 100, decimals=2)
+    print(">> {}: top-{} label recall {}".format(dataset, _head_array(heads).shape[1],
+                                                 r(recalls[0]) if len(recalls) == 1 else "E: {}, M: {}, H: {}".format(*map(r, recalls))))
+    return _WithStats(out, stats)
+
+
+def label_recall(stats):
+    """Mean over the queries with a positive among the database rows of ``found / rows`` (NaN without such a query)."""
+    live = stats["rows"] > 0
+    return float(np.mean(stats["found"][live] / stats["rows"][live])) if live.any() else float("nan")

@@ -2267,6 +2267,46 @@ def knn_reverse_merge(ids, scores):
     return knn_reverse_apply(ids, scores, offsets, offers)
 
 
+# ------------------------------------------------------------------ top-K lists, overlap (include/mdx_overlap.h)
+
+OVERLAP_MAX_K = RESCORE_MAX_K     # include/mdx_overlap.h MDX_OVERLAP_MAX_K: the longest list of any search here
+OVERLAP_MAX_DEPTHS = 8            # include/mdx_overlap.h MDX_OVERLAP_MAX_DEPTHS
+
+
+def topk_overlap(a, b, depths):
+    """``out`` int32 ``[nq, T]``: ``out[q, t]`` = the ids ``>= 0`` among the first ``min(depths[t], ka)`` entries of ``a[q]`` that also
+    occur among the first ``min(depths[t], kb)`` entries of ``b[q]`` (``mdx_topk_overlap``; the definition is in
+    ``include/mdx_overlap.h``).  ``a`` int64 ``[nq, ka]`` and ``b`` int64 ``[nq, kb]`` on one device, contiguous, ``1 <= ka, kb <=
+    OVERLAP_MAX_K``; the ids ``>= 0`` of a row are distinct and negative ids are padding.  ``depths``: 1 to ``OVERLAP_MAX_DEPTHS``
+    positive ascending integers.  An id at or above 2^31 is a ``ValueError`` -- the one read-back of this wrapper (the largest id of
+    ``a`` and ``b``), left out while the current stream is capturing, where the kernel counts such an id as padding."""
+    who = "topk_overlap"
+    _kmeans_tensor(a, torch.int64, who, "a", 2)
+    nq, ka = a.shape
+    _ivf_vector(a, torch.int64, who, "a", (nq, ka), a.device)
+    _kmeans_tensor(b, torch.int64, who, "b", 2)
+    kb = b.shape[1]
+    _ivf_vector(b, torch.int64, who, "b", (nq, kb), a.device)
+    if max(ka, kb) > OVERLAP_MAX_K:
+        raise ValueError("%s: ka = %d and kb = %d must be at most OVERLAP_MAX_K = %d" % (who, ka, kb, OVERLAP_MAX_K))
+    depths = list(depths) if isinstance(depths, (list, tuple)) else [depths]
+    if not 1 <= len(depths) <= OVERLAP_MAX_DEPTHS:
+        raise ValueError("%s: between 1 and %d depths, got %d" % (who, OVERLAP_MAX_DEPTHS, len(depths)))
+    for t, x in enumerate(depths):
+        _ivf_count(x, who, "depths[%d]" % t)
+        if x >= 1 << 31 or (t and x < depths[t - 1]):
+            raise ValueError("%s: depths must be ascending and below 2^31, got %r" % (who, depths))
+    if not torch.cuda.is_current_stream_capturing():
+        top = max(int(a.max()), int(b.max()))
+        if top >= 1 << 31:
+            raise ValueError("%s: id %d is at or above 2^31" % (who, top))
+    out = torch.empty((nq, len(depths)), dtype=torch.int32, device=a.device)
+    with _on(a):
+        check(_lib.lib().mdx_topk_overlap(_vp(a.data_ptr()), ka, _vp(b.data_ptr()), kb, nq, (ctypes.c_int32 * len(depths))(*depths),
+                                          len(depths), _vp(out.data_ptr()), _stream()), "mdx_topk_overlap")
+    return out
+
+
 def _csr(id_lists, device):
     arrays =[np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)

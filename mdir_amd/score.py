@@ -40,6 +40,23 @@ enabled keys, ``reverse`` to true; ``iters`` and ``seed`` go to ``cluster.kmeans
 ``truncate`` best rows by the Jaccard overlap of k-reciprocal codes (``rerank.k_reciprocal``), after DBA when both are set;
 with ``query_expansion`` the expanded queries' scores are its first stage; not together with ``diffusion`` or ``rescore``;
 single-process only; it honours ``neighbours: i8``.
+``search: {index: exact | i8 | f16 | ivf | ivfpq, depth: K, ...}`` (criterion key, not in the reference; ``1 <= K <= 4096``, clamped to
+N; single-process only) evaluates the top-``K`` lists an index returns instead of a ranking of every row: the index is built on
+``vecs``, searched with ``qvecs``, and the ``[Q, K]`` ids go through ``evaluate.compute_map_and_print_topk`` -- the AP of a top-K list
+is the left-to-right partial sum of the full ranking's AP with the reference's normaliser ``len(ok)`` (NOT ``min(len(ok), K)``), so
+``K = N`` reproduces the reference bit for bit; P@kappa is NaN where the list does not determine it; one more ``>>`` line prints the
+label recall.  The printed and logged keys are the reference's.  Routes: ``exact`` -- ``ops.topk`` of the exact scores; ``i8`` /
+``f16`` with ``shortlist`` (required) and ``exact`` (default false) -- ``search.search`` on a ``DescriptorIndex`` of that storage;
+``ivf`` with ``lists`` and ``nprobe`` (required), ``storage: f32 | i8`` (default ``i8``), ``shortlist`` / ``exact`` (int8 only),
+``iters`` / ``seed`` (to ``cluster.kmeans``) -- ``IVFIndex.train`` and its ``search``; ``ivfpq`` with ``lists`` and ``nprobe``
+(required), ``m`` (default 64), ``refine: i8``, ``shortlist``, ``rescore``, ``iters`` / ``seed`` -- ``IVFPQIndex.train`` and its
+``search`` (the index keeps the fp32 rows only where ``shortlist`` / ``rescore`` read them).  A ``shortlist`` is at least ``depth``.
+``recall: true`` (default false) also computes the exact top-``K`` -- one full scan -- and prints ``recall@K`` against it, min / mean
+over the queries (``search.recall_at``, ``ops.topk_overlap``).  Not together with ``ranking: full``, ``rescore``, ``query_expansion``,
+``diffusion``, ``k_reciprocal`` or a ``storage`` / ``similarity`` other than the default (the route chooses how the rows are kept);
+``database_augmentation`` is allowed and runs first.  The ``dataset`` times gain the laps ``build_index`` and ``search`` in front of
+``compute_score``.  ``CirDatasetAp.searched_map(vecs, qvecs)`` is the part after extraction; the index, the search's result, the
+evaluation's stats and the recall stay reachable as ``last_index``, ``last_search``, ``last_stats`` and ``last_recall``.
 """
 import contextlib
 import gzip
@@ -50,10 +67,13 @@ import os.path
 from collections import OrderedDict
 
 import numpy as np
+import torch
 
-from . import ivf, ops, rerank
+from . import ivf, ivfpq, ops, rerank
+from . import search as _search
 from .datasets import configdataset, get_data_root, initialize_transforms
-from .evaluate import compute_map_and_print, compute_map_and_print_composite, compute_map_and_print_from_scores
+from .evaluate import (compute_map_and_print, compute_map_and_print_composite, compute_map_and_print_from_scores,
+                       compute_map_and_print_topk)
 from .networks import extract_vectors_device
 from .scenario import StopWatch, path_join
 from .trace import range_
@@ -103,6 +123,8 @@ def _read_table(path, keys=None):
 
 
 class CirDatasetAp:
+    search = last_search = last_index = last_recall = last_stats = None      # the `search` key: off; what its last run left
+
     def __init__(self, params):
         self.image_size = params.pop("image_size")
         self.dataset = params.pop("dataset")
@@ -157,6 +179,17 @@ class CirDatasetAp:
             others = [k for k in ("query_expansion", "database_augmentation", "diffusion", "k_reciprocal") if getattr(self, k)]
             if others:
                 raise ValueError("rescore together with %s is not supported" % " / ".join(others))
+        # top-K lists of an index, evaluated as truncated rankings (not in the reference): {index, depth, ...}; None = off
+        self.search = _search_params(params.pop("search", None))
+        if self.search:
+            if self.ranking == "full":
+                raise ValueError("search together with ranking: full is not supported: a top-K list is not a full ranking")
+            for key in ("rescore", "query_expansion", "diffusion", "k_reciprocal"):
+                if getattr(self, key):
+                    raise ValueError("search together with %s is not supported" % key)
+            if self.storage != "f32" or self.similarity != "exact":
+                raise ValueError("search together with storage: %s / similarity: %s is not supported: search: {index: ...} chooses "
+                                 "how the rows are kept" % (self.storage, self.similarity))
         if isinstance(self.dataset, dict):
             assert self.dataset.keys() == {"name", "queries", "db", "imgdir"}
             imgdir = self.dataset["imgdir"]
@@ -190,6 +223,9 @@ class CirDatasetAp:
                              "%d ranks" % (self.dataset, _world_size()))
         if _world_size() > 1 and self.rescore:
             raise ValueError("%s: rescore runs in a single process for now; this run has %d ranks" % (self.dataset, _world_size()))
+        if _world_size() > 1 and self.search:
+            raise ValueError("%s: search builds and searches its index in a single process; this run has %d ranks"
+                             % (self.dataset, _world_size()))
         if _world_size() > 1:
             # one process per GPU (torchrun eval.py ...): every rank extracts its slice of the
             # database, which stays resident as its shard; same rows go to the logger on every rank
@@ -213,6 +249,12 @@ class CirDatasetAp:
         stopwatch.lap("extract_descriptors")
 
         print(">> {}: Evaluating...".format(self.dataset))
+        if self.search:
+            with range_("%s/compute_score" % self.dataset):
+                averages, scores_per_query = self.searched_map(vecs, qvecs, lap=stopwatch.lap)
+            stopwatch.lap("compute_score")
+            self._log(logger, stopwatch, averages, scores_per_query)
+            return
         with range_("%s/compute_score" % self.dataset):
             # one evaluation multiplies the database once: the exact product reads `vecs` [N,D] where it lies
             # (mdx_scores_rowmajor: same kernels and bits as on an index, no 8 GB re-tiled copy); the fp16 shard and the
@@ -281,6 +323,49 @@ class CirDatasetAp:
                 ranks[:, :K] = ids
             return compute_map_and_print(self.dataset, ranks.t(), self.gnd)
         return compute_map_and_print_composite(self.dataset, scores, ids, self.gnd)
+
+    def searched_map(self, vecs, qvecs, lap=None):
+        """The ``search`` key after extraction: ``(averages, per_query)`` of the top-``depth`` lists that the chosen index returns
+        for ``qvecs`` fp32 ``[Q, D]`` against ``vecs`` fp32 ``[N, D]`` (device tensors, as the existing path holds them), through
+        ``compute_map_and_print_topk``.  DBA, if set, changes ``vecs`` first.  ``lap(name)`` is called, after a device
+        synchronisation, when the index is built (``build_index``) and when the lists are there (``search``).  The index
+        (closed on the way out, on errors too), the search's result, the evaluation's ``.stats`` and, with ``recall: true``, the
+        per-query recall against the exact top-``depth`` stay reachable as ``last_index``, ``last_search``, ``last_stats`` and
+        ``last_recall``."""
+        p = self.search
+        self.last_search = self.last_index = self.last_recall = self.last_stats = None
+
+        def mark(name):
+            if lap is not None:
+                torch.cuda.synchronize(vecs.device)
+                lap(name)
+
+        if self.database_augmentation:
+            with range_("database_augmentation"):
+                with _neighbour_index(vecs, self.neighbours) as nix:
+                    vecs = rerank.database_augmentation(vecs, index=nix, **self.database_augmentation)
+        n = vecs.shape[0]
+        depth = min(p["depth"], n)
+        index = None
+        try:
+            with range_("build_index"):
+                index = self.last_index = _search_index(p, vecs)
+            mark("build_index")
+            with range_("search"):
+                res = self.last_search = _search_lists(p, index, vecs, qvecs, depth)
+            mark("search")
+            out = compute_map_and_print_topk(self.dataset, res.ids, self.gnd, n)
+            self.last_stats = getattr(out, "stats", None)               # (None: a dataset the reference does not evaluate)
+            if p["recall"]:
+                with range_("recall"):
+                    exact_ids, _ = ops.topk(_exact_scores(vecs, qvecs), depth)
+                    self.last_recall = _search.recall_at(res.ids, exact_ids, depth)[:, 0]
+                print(">> {}: recall@{} against the exact top-{}: min {:.4f} / mean {:.4f}".format(
+                    self.dataset, depth, depth, float(np.min(self.last_recall)), float(np.mean(self.last_recall))))
+        finally:
+            if index is not None:
+                index.close()
+        return out
 
     @staticmethod
     def _log(logger, stopwatch, averages, scores_per_query):
@@ -443,6 +528,118 @@ def _rescore_params(value):
     if isinstance(x, bool) or not isinstance(x, int) or not 1 <= x <= ops.RESCORE_MAX_K:
         raise ValueError("rescore: shortlist must be an integer in [1, %d], got %r" % (ops.RESCORE_MAX_K, x))
     return {"shortlist": x}
+
+
+_SEARCH_KEYS = {
+    "exact": ("index", "depth", "recall"),
+    "i8": ("index", "depth", "recall", "shortlist", "exact"),
+    "f16": ("index", "depth", "recall", "shortlist", "exact"),
+    "ivf": ("index", "depth", "recall", "lists", "nprobe", "storage", "shortlist", "exact", "iters", "seed"),
+    "ivfpq": ("index", "depth", "recall", "lists", "nprobe", "m", "refine", "shortlist", "rescore", "iters", "seed"),
+}
+
+
+def _search_params(value):
+    """``{index, depth, ...}`` of the ``search`` criterion key with its defaults filled in, validated (None: the key is absent).
+    The limits are those of the index classes (``ops.RESCORE_MAX_K``, ``ops.PQ_MAX_M``, ``ivf.STORAGES``, ``ivfpq.REFINES``)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict) or not isinstance(value.get("index"), str) or value["index"] not in _SEARCH_KEYS:
+        raise ValueError("search: a mapping {index: %s, depth: K, ...}, got %r" % (" | ".join(_SEARCH_KEYS), value))
+    kind = value["index"]
+    allowed = _SEARCH_KEYS[kind]
+    unknown = set(value) - set(allowed)
+    if unknown:
+        raise ValueError("search: index: %s: unknown keys %s (allowed: %s)" % (kind, sorted(unknown, key=str), ", ".join(allowed)))
+    required = ("depth",) + {"exact": (), "i8": ("shortlist",), "f16": ("shortlist",)}.get(kind, ("lists", "nprobe"))
+    for key in required:
+        if key not in value:
+            raise ValueError("search: index: %s: %s is required" % (kind, key))
+    out = dict(value)
+
+    def integer(key, lo, hi=None):
+        x = out[key]
+        if isinstance(x, bool) or not isinstance(x, int) or x < lo or (hi is not None and x > hi):
+            raise ValueError("search: %s must be an integer %s, got %r" % (key, ">= %d" % lo if hi is None else "in [%d, %d]" % (lo, hi), x))
+
+    def boolean(key):
+        out.setdefault(key, False)
+        if not isinstance(out[key], bool):
+            raise ValueError("search: %s must be true or false, got %r" % (key, out[key]))
+
+    integer("depth", 1, ops.RESCORE_MAX_K)
+    boolean("recall")
+    for key in ("lists", "nprobe", "iters"):
+        if key in out:
+            integer(key, 1)
+    if "seed" in out:
+        integer("seed", 0)
+    if "nprobe" in out and out["nprobe"] > out["lists"]:
+        raise ValueError("search: 1 <= nprobe <= lists is required, got nprobe=%d lists=%d" % (out["nprobe"], out["lists"]))
+    if "shortlist" in allowed:
+        out.setdefault("shortlist", None)
+        if out["shortlist"] is not None:
+            integer("shortlist", out["depth"], ops.RESCORE_MAX_K)
+    if kind == "ivf":
+        out.setdefault("storage", "i8")
+        if out["storage"] not in ivf.STORAGES:
+            raise ValueError("search: storage must be 'f32' or 'i8', got %r" % (out["storage"],))
+    if "exact" in allowed:
+        boolean("exact")
+        if kind == "ivf" and out["storage"] == "f32" and (out["shortlist"] is not None or out["exact"]):
+            raise ValueError("search: shortlist and exact need storage: i8 (the fp32 lists are scored exactly)")
+        if out["exact"] and out["shortlist"] is None:
+            raise ValueError("search: exact: true needs a shortlist")
+    if kind == "ivfpq":
+        out.setdefault("m", 64)
+        integer("m", 1, ops.PQ_MAX_M)
+        out.setdefault("refine", None)
+        if out["refine"] is not None and not (isinstance(out["refine"], str) and out["refine"] in ivfpq.REFINES):
+            raise ValueError("search: refine must be 'i8' or absent, got %r" % (out["refine"],))
+        out.setdefault("rescore", None)
+        if out["rescore"] is not None:
+            if out["refine"] is None or out["shortlist"] is None:
+                raise ValueError("search: rescore needs refine: i8 and a shortlist")
+            integer("rescore", out["depth"], out["shortlist"])
+    return out
+
+
+def _exact_scores(vecs, qvecs):
+    """fp32 ``[Q, N]``: the exact chain scores, read from ``vecs`` where it lies, or through an fp32 index where D % 4 != 0."""
+    if vecs.shape[1] % 4 == 0:
+        return ops.scores_rowmajor(vecs, qvecs, "ND")
+    index = ops.DescriptorIndex(vecs, "ND")
+    try:
+        return index.scores(qvecs, "ND")
+    finally:
+        index.close()
+
+
+def _search_index(p, vecs):
+    """The index of the ``search`` key over ``vecs`` (None for ``index: exact``); the caller closes it."""
+    kind = p["index"]
+    if kind == "exact":
+        return None
+    if kind in ("i8", "f16"):
+        return ops.DescriptorIndex(vecs, "ND", storage=kind)
+    kmeans = {key: p[key] for key in ("iters", "seed") if key in p}
+    if kind == "ivf":
+        return ivf.IVFIndex.train(vecs, p["lists"], storage=p["storage"], **kmeans)
+    keep_rows = p["shortlist"] is not None and (p["refine"] is None or p["rescore"] is not None)
+    return ivfpq.IVFPQIndex.train(vecs, p["lists"], m=p["m"], kmeans=kmeans, keep_rows=keep_rows, refine=p["refine"])
+
+
+def _search_lists(p, index, vecs, qvecs, depth):
+    """The result of the route's search, a named tuple whose ``ids`` are int64 ``[Q, depth]``."""
+    kind = p["index"]
+    if kind == "exact":
+        ids, scores = ops.topk(_exact_scores(vecs, qvecs), depth)
+        return _search.SearchResult(ids, scores, None, torch.empty(0, dtype=torch.int64, device=ids.device))
+    if kind in ("i8", "f16"):
+        return _search.search(index, vecs, qvecs, depth, p["shortlist"], exact=p["exact"])
+    if kind == "ivf":
+        return index.search(qvecs, depth, p["nprobe"], shortlist=p["shortlist"], exact=p["exact"])
+    return index.search(qvecs, depth, p["nprobe"], shortlist=p["shortlist"], rescore=p["rescore"])
 
 
 def _rank_world():

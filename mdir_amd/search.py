@@ -29,9 +29,13 @@ an fp32 index) + ``topk`` on chunks of rows.  Both routes return the same bits.
 the connected components of the self-join's graph, at up to 8 thresholds from one pass of the join kernel, as a :data:`Groups`.
 The candidates of each chunk go straight into a lock-free union-find on the device (``include/mdx.h``, "near-duplicate groups") and
 are dropped again: N integers per threshold are kept, never a pair list.  Both routes return the same labels.
+
+``recall_at(found_ids, exact_ids, depths)`` is how good a set of top-K lists is against another, usually the exact one: per query and
+depth the share of the exact head that the found head holds, from the counts of ``ops.topk_overlap`` (``include/mdx_overlap.h``).
 """
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -438,3 +442,15 @@ def duplicate_groups(index, rows, threshold, chunk=None, max_candidates=1 << 26)
     if single:
         return Groups(labels[0], csr[0][0], csr[0][1], stats)
     return Groups(labels, [c[0] for c in csr], [c[1] for c in csr], stats)
+
+
+def recall_at(found_ids, exact_ids, depths):
+    """Recall of the lists ``found_ids`` int64 ``[nq, ka]`` against ``exact_ids`` int64 ``[nq, kb]`` (device tensors, best first, -1
+    padding) at each of ``depths`` (an integer or 1 to ``ops.OVERLAP_MAX_DEPTHS`` ascending ones): float64 ``[nq, T]`` on the host,
+    ``ops.topk_overlap(found_ids, exact_ids, depths)[q, t] / min(depths[t], valid entries of exact_ids[q])`` -- the share of the
+    exact head that the found head holds; NaN for a query whose exact list is all padding."""
+    depths = list(depths) if isinstance(depths, (list, tuple)) else [depths]
+    counts = ops.topk_overlap(found_ids, exact_ids, depths).cpu().numpy().astype("float64")
+    valid = (exact_ids >= 0).sum(1).cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return counts / np.minimum(np.asarray(depths, dtype=np.int64)[None, :], valid[:, None])
