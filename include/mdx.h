@@ -1076,6 +1076,19 @@ int mdx_range_select(const float *scores, int64_t m, int64_t n, int64_t ld, floa
  * tests/test_gpu_overlap_memcontract.py).  An addition: MDX_ABI_VERSION stays. */
 #include "mdx_overlap.h"
 
+/* ------------------------------- graph index */
+
+/* The fourth family of index beside the scan, the inverted file and IVF-PQ: a best-first walk over a fixed-degree neighbour graph of
+ * the database (mdir_amd/graph.py, GraphIndex; the `search` criterion key of mdir_amd/score.py, index: graph).  The graph is made of
+ * the kNN lists the library already builds (search.knn_join, IVFIndex.knn_join), pruned by rank-based detour counts and completed with
+ * reverse edges.  mdx_graph_search walks it, one workgroup per query, with exact chain scores -- the bits of mdx_scores -- so that no
+ * rescoring stage follows; mdx_graph_detours is the integer kernel of the build.  The whole contract -- the sequential definition of
+ * the walk, why a visited-row table cannot change it, the LDS footprint, the launch shapes, the refusals -- is stated in mdx_graph.h,
+ * beside this file, with the prototypes; their names are in _lib.GRAPH_EXPORTS, for the reason given above for mdx_knn_join.h, and
+ * their census is tests/test_graph_host.py (exported, bound, and covered by tests/test_gpu_graph_memcontract.py).
+ * Additions: MDX_ABI_VERSION stays. */
+#include "mdx_graph.h"
+
 /* ------------------------------------------------- whitening learning (float64) */
 
 /* The dense products of whitenlearn / pcawhitenlearn (mdir/external/cirtorch/utils/whiten.py:14-53), which the

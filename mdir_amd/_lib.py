@@ -36,7 +36,7 @@ ABI_VERSION = 3        # include/mdx.h MDX_ABI_VERSION this binding was written 
 def build(force=False):
     """Compile libmdx.so with hipcc --offload-arch=gfx950 (see csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h", "mdx_groups.h", "mdx_krecip.h", "mdx_photometric.h", "mdx_train.h", "mdx_kmeans.h", "mdx_ivf.h", "mdx_lists_i8.h", "mdx_lists_pq.h", "mdx_lists_edit.h", "mdx_refine.h", "mdx_knn_reverse.h", "mdx_unet.h", "mdx_overlap.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("mdx.h", "mdx_knn_join.h", "mdx_trunk_f16.h", "mdx_groups.h", "mdx_krecip.h", "mdx_photometric.h", "mdx_train.h", "mdx_kmeans.h", "mdx_ivf.h", "mdx_lists_i8.h", "mdx_lists_pq.h", "mdx_lists_edit.h", "mdx_refine.h", "mdx_knn_reverse.h", "mdx_unet.h", "mdx_overlap.h", "mdx_graph.h")]
     stale = not os.path.exists(LIB_PATH) or \
         any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -143,6 +143,8 @@ def _declare(lib):
         "mdx_knn_reverse_merge": (i32, [p, p, i64, i64, p, p, i64, p, p, p, p]),
         "mdx_bn_act_into": (i32, [p, p, i64, i64, i64, i64, p, p, p, p, f32, i32, f32, p]),
         "mdx_topk_overlap": (i32, [p, i64, p, i64, i64, ctypes.POINTER(ctypes.c_int32), i64, p, p]),
+        "mdx_graph_search": (i32, [p, i64, i64, i64, p, i64, p, i64, i32, p, p, i64, i64, i64, i64, i64, i32, p, p, p, p, p]),
+        "mdx_graph_detours": (i32, [p, i64, i64, p, p]),
         "mdx_bn_act_f16": (i32, [p, p, i64, i64, i64, p, p, p, p, f32, i32, p]),
         "mdx_pool_l2n_f16": (i32, [p, i32, i32, i32, i32, i32, f32, f32, f32, p, p]),
         "mdx_pool_multi_f16": (i32, [pp, i32, i32, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), i32, f32, f32, p, p]),
@@ -279,6 +281,10 @@ MDX_ACT_NONE, MDX_ACT_RELU, MDX_ACT_LEAKY = 0, 1, 2            # include/mdx_une
 # include/mdx_overlap.h (included by mdx.h): the overlap of two sets of top-K lists, apart from EXPORTS for the same reason; the census
 # of these is tests/test_overlap_host.py (include/mdx.h, "top-K lists, overlap")
 OVERLAP_EXPORTS = ("mdx_topk_overlap",)
+
+# include/mdx_graph.h (included by mdx.h): the graph index, apart from EXPORTS for the same reason; the census of these is
+# tests/test_graph_host.py (include/mdx.h, "graph index")
+GRAPH_EXPORTS = ("mdx_graph_search", "mdx_graph_detours")
 
 
 def lib():

@@ -2307,6 +2307,84 @@ def topk_overlap(a, b, depths):
     return out
 
 
+# ------------------------------------------------------------------ graph index (include/mdx_graph.h)
+
+GRAPH_MAX_D = 8192                # include/mdx_graph.h MDX_GRAPH_MAX_D: the centred query stays in 32 KiB of LDS
+GRAPH_MAX_DEGREE = 64             # MDX_GRAPH_MAX_DEGREE
+GRAPH_MAX_SEEDS = 512             # MDX_GRAPH_MAX_SEEDS
+GRAPH_MAX_BEAM = 512              # MDX_GRAPH_MAX_BEAM
+GRAPH_MAX_WIDTH = 8               # MDX_GRAPH_MAX_WIDTH
+GRAPH_MAX_CANDIDATES = 512        # MDX_GRAPH_MAX_CANDIDATES: width * degree of one step, = GRAPH_MAX_WIDTH * GRAPH_MAX_DEGREE
+GRAPH_MAX_K0 = 128                # MDX_GRAPH_MAX_K0: the longest list of graph_detours
+
+
+def graph_search(rows, graph, queries, seeds, k, beam, width=1, max_steps=None, qlayout="ND", center=None, table_bits=0):
+    """``(ids int64 [nq, k], scores fp32 [nq, k], steps int32 [nq], scored int32 [nq])``: the beam search of every query over the
+    neighbour graph ``graph`` (int32 ``[n, R]``, contiguous; entries outside ``[0, n)`` are padding) of ``rows`` (fp32 ``[n, d]`` on
+    the device, rows contiguous at any stride), from ``seeds`` (int64 ``[nq, S]``) -- ``mdx_graph_search``; the sequential definition
+    is in ``include/mdx_graph.h``.  ``beam`` is the beam length L (``k <= L <= GRAPH_MAX_BEAM``), ``width`` the parents per step,
+    ``max_steps`` the step limit (default ``ceil(4 * beam / width)``).  Every score is bit-identical to
+    ``DescriptorIndex(rows, "ND").scores(queries, qlayout, center)`` at the same id (a NaN score is the quiet NaN); the tail of a row
+    is padded with -1 and NaN.  ``table_bits`` sizes the table of rows already scored and changes only ``scored``."""
+    who = "graph_search"
+    rp, ld = _kmeans_matrix(rows, who, "rows")
+    n, d = rows.shape
+    _kmeans_tensor(graph, torch.int32, who, "graph", 2)
+    R = graph.shape[1]
+    _ivf_vector(graph, torch.int32, who, "graph", (n, R), rows.device)
+    _kmeans_tensor(queries, torch.float32, who, "queries", 2)
+    nq, dq, lay = _layout(queries, qlayout, "queries")
+    if dq != d or not queries.is_contiguous() or queries.device != rows.device:
+        raise ValueError("%s: queries must be contiguous with dimension %d on %s, got %s (%s) on %s" % (
+            who, d, rows.device, tuple(queries.shape), qlayout, queries.device))
+    if center is not None:
+        _ivf_vector(center, torch.float32, who, "center", (d,), rows.device)
+    _kmeans_tensor(seeds, torch.int64, who, "seeds", 2)
+    S = seeds.shape[1]
+    _ivf_vector(seeds, torch.int64, who, "seeds", (nq, S), rows.device)
+    for x, what in ((k, "k"), (beam, "beam"), (width, "width")):
+        _ivf_count(x, who, what)
+    if max_steps is None:
+        max_steps = -(-4 * beam // width)
+    _ivf_count(max_steps, who, "max_steps")
+    _ivf_count(table_bits, who, "table_bits", 0)
+    if d > GRAPH_MAX_D or R > GRAPH_MAX_DEGREE or S > GRAPH_MAX_SEEDS:
+        raise ValueError("%s: d = %d, degree = %d and seeds = %d must be at most %d, %d and %d" % (
+            who, d, R, S, GRAPH_MAX_D, GRAPH_MAX_DEGREE, GRAPH_MAX_SEEDS))
+    if not k <= beam <= GRAPH_MAX_BEAM:
+        raise ValueError("%s: beam = %d must be in [k = %d, GRAPH_MAX_BEAM = %d]" % (who, beam, k, GRAPH_MAX_BEAM))
+    if width > GRAPH_MAX_WIDTH:                       # with it, width * degree <= GRAPH_MAX_CANDIDATES
+        raise ValueError("%s: width = %d must be at most %d" % (who, width, GRAPH_MAX_WIDTH))
+    if table_bits and not 8 <= table_bits <= 14:
+        raise ValueError("%s: table_bits = %d must be 0 or in [8, 14]" % (who, table_bits))
+    ids = torch.empty((nq, k), dtype=torch.int64, device=rows.device)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=rows.device)
+    steps = torch.empty((nq,), dtype=torch.int32, device=rows.device)
+    scored = torch.empty((nq,), dtype=torch.int32, device=rows.device)
+    with _on(rows):
+        check(_lib.lib().mdx_graph_search(rp, n, d, ld, _vp(graph.data_ptr()), R, _vp(queries.data_ptr()), nq, lay,
+                                          None if center is None else _vp(center.data_ptr()), _vp(seeds.data_ptr()), S, k, beam, width,
+                                          max_steps, table_bits, _vp(ids.data_ptr()), _vp(scores.data_ptr()), _vp(steps.data_ptr()),
+                                          _vp(scored.data_ptr()), _stream()), "mdx_graph_search")
+    return ids, scores, steps, scored
+
+
+def graph_detours(lists):
+    """``detours`` int32 ``[n, K0]`` of the neighbour lists ``lists`` (int64 ``[n, K0]`` on the device, contiguous, best first, own id
+    removed, entries outside ``[0, n)`` padding, ``K0 <= GRAPH_MAX_K0``): for a valid ``b = lists[i, j]`` the ranks ``t < j`` whose
+    ``a = lists[i, t]`` lists ``b`` before rank ``j``; ``K0`` for an invalid entry (``mdx_graph_detours``)."""
+    who = "graph_detours"
+    _kmeans_tensor(lists, torch.int64, who, "lists", 2)
+    n, k0 = lists.shape
+    _ivf_vector(lists, torch.int64, who, "lists", (n, k0), lists.device)
+    if k0 > GRAPH_MAX_K0:
+        raise ValueError("%s: K0 = %d > GRAPH_MAX_K0 = %d" % (who, k0, GRAPH_MAX_K0))
+    out = torch.empty((n, k0), dtype=torch.int32, device=lists.device)
+    with _on(lists):
+        check(_lib.lib().mdx_graph_detours(_vp(lists.data_ptr()), n, k0, _vp(out.data_ptr()), _stream()), "mdx_graph_detours")
+    return out
+
+
 def _csr(id_lists, device):
     arrays =[np.asarray(ids, dtype=np.int64).reshape(-1) for ids in id_lists]
     offsets = np.zeros(len(arrays) + 1, dtype=np.int64)

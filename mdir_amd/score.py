@@ -40,7 +40,7 @@ enabled keys, ``reverse`` to true; ``iters`` and ``seed`` go to ``cluster.kmeans
 ``truncate`` best rows by the Jaccard overlap of k-reciprocal codes (``rerank.k_reciprocal``), after DBA when both are set;
 with ``query_expansion`` the expanded queries' scores are its first stage; not together with ``diffusion`` or ``rescore``;
 single-process only; it honours ``neighbours: i8``.
-``search: {index: exact | i8 | f16 | ivf | ivfpq, depth: K, ...}`` (criterion key, not in the reference; ``1 <= K <= 4096``, clamped to
+``search: {index: exact | i8 | f16 | ivf | ivfpq | graph, depth: K, ...}`` (criterion key, not in the reference; ``1 <= K <= 4096``, clamped to
 N; single-process only) evaluates the top-``K`` lists an index returns instead of a ranking of every row: the index is built on
 ``vecs``, searched with ``qvecs``, and the ``[Q, K]`` ids go through ``evaluate.compute_map_and_print_topk`` -- the AP of a top-K list
 is the left-to-right partial sum of the full ranking's AP with the reference's normaliser ``len(ok)`` (NOT ``min(len(ok), K)``), so
@@ -50,7 +50,12 @@ label recall.  The printed and logged keys are the reference's.  Routes: ``exact
 ``ivf`` with ``lists`` and ``nprobe`` (required), ``storage: f32 | i8`` (default ``i8``), ``shortlist`` / ``exact`` (int8 only),
 ``iters`` / ``seed`` (to ``cluster.kmeans``) -- ``IVFIndex.train`` and its ``search``; ``ivfpq`` with ``lists`` and ``nprobe``
 (required), ``m`` (default 64), ``refine: i8``, ``shortlist``, ``rescore``, ``iters`` / ``seed`` -- ``IVFPQIndex.train`` and its
-``search`` (the index keeps the fp32 rows only where ``shortlist`` / ``rescore`` read them).  A ``shortlist`` is at least ``depth``.
+``search`` (the index keeps the fp32 rows only where ``shortlist`` / ``rescore`` read them); ``graph`` with ``degree`` and ``beam``
+(required; ``depth <= beam <= 512``, so a ``depth`` above 512 is refused on this route), ``k0`` (default ``2 * degree``), ``width``
+(default 1), ``seeds`` (default 8), ``entries: sample | medoids`` (default ``sample``) with ``n_entries`` (default 1024) or, for the
+medoids, ``lists`` (required) and ``iters`` of the k-means behind them, ``seed``, and ``neighbours: exact | i8 | {ivf: {...}}`` in the
+grammar of the ``neighbours`` key (default ``exact``) -- ``graph.GraphIndex.build`` and its ``search``, a beam search over a pruned
+kNN graph with exact chain scores.  A ``shortlist`` is at least ``depth``.
 ``recall: true`` (default false) also computes the exact top-``K`` -- one full scan -- and prints ``recall@K`` against it, min / mean
 over the queries (``search.recall_at``, ``ops.topk_overlap``).  Not together with ``ranking: full``, ``rescore``, ``query_expansion``,
 ``diffusion``, ``k_reciprocal`` or a ``storage`` / ``similarity`` other than the default (the route chooses how the rows are kept);
@@ -69,7 +74,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import ivf, ivfpq, ops, rerank
+from . import cluster, graph, ivf, ivfpq, ops, rerank
 from . import search as _search
 from .datasets import configdataset, get_data_root, initialize_transforms
 from .evaluate import (compute_map_and_print, compute_map_and_print_composite, compute_map_and_print_from_scores,
@@ -536,7 +541,10 @@ _SEARCH_KEYS = {
     "f16": ("index", "depth", "recall", "shortlist", "exact"),
     "ivf": ("index", "depth", "recall", "lists", "nprobe", "storage", "shortlist", "exact", "iters", "seed"),
     "ivfpq": ("index", "depth", "recall", "lists", "nprobe", "m", "refine", "shortlist", "rescore", "iters", "seed"),
+    "graph": ("index", "depth", "recall", "degree", "k0", "beam", "width", "seeds", "entries", "n_entries", "lists", "iters", "seed",
+              "neighbours"),
 }
+_GRAPH_ENTRIES = ("sample", "medoids")
 
 
 def _search_params(value):
@@ -551,7 +559,7 @@ def _search_params(value):
     unknown = set(value) - set(allowed)
     if unknown:
         raise ValueError("search: index: %s: unknown keys %s (allowed: %s)" % (kind, sorted(unknown, key=str), ", ".join(allowed)))
-    required = ("depth",) + {"exact": (), "i8": ("shortlist",), "f16": ("shortlist",)}.get(kind, ("lists", "nprobe"))
+    required = ("depth",) + {"exact": (), "i8": ("shortlist",), "f16": ("shortlist",), "graph": ("degree", "beam")}.get(kind, ("lists", "nprobe"))
     for key in required:
         if key not in value:
             raise ValueError("search: index: %s: %s is required" % (kind, key))
@@ -601,6 +609,40 @@ def _search_params(value):
             if out["refine"] is None or out["shortlist"] is None:
                 raise ValueError("search: rescore needs refine: i8 and a shortlist")
             integer("rescore", out["depth"], out["shortlist"])
+    if kind == "graph":
+        if out["depth"] > ops.GRAPH_MAX_BEAM:
+            raise ValueError("search: index: graph: depth = %d is above the beam limit %d (the lists are the head of the beam)"
+                             % (out["depth"], ops.GRAPH_MAX_BEAM))
+        integer("degree", 1, ops.GRAPH_MAX_DEGREE)
+        out.setdefault("k0", 2 * out["degree"])
+        integer("k0", 1, ops.GRAPH_MAX_K0)
+        integer("beam", out["depth"], ops.GRAPH_MAX_BEAM)
+        out.setdefault("width", 1)
+        integer("width", 1, ops.GRAPH_MAX_WIDTH)
+        out.setdefault("seeds", 8)
+        integer("seeds", 1, ops.GRAPH_MAX_SEEDS)
+        out.setdefault("entries", "sample")
+        if not (isinstance(out["entries"], str) and out["entries"] in _GRAPH_ENTRIES):
+            raise ValueError("search: entries must be 'sample' or 'medoids', got %r" % (out["entries"],))
+        if out["entries"] == "medoids":
+            if "lists" not in out:
+                raise ValueError("search: index: graph: entries: medoids needs lists (the k-means behind them)")
+            if "n_entries" in out:
+                raise ValueError("search: n_entries goes with entries: sample (the medoids are one per non-empty list)")
+        else:
+            if "lists" in out or "iters" in out:
+                raise ValueError("search: index: graph: lists and iters go with entries: medoids")
+            out.setdefault("n_entries", 1024)
+            integer("n_entries", 1)
+        out.setdefault("neighbours", "exact")
+        nb = out["neighbours"]
+        if isinstance(nb, dict):
+            out["neighbours"] = _ivf_neighbours_params(nb, [out["k0"] + 1])
+        elif not (isinstance(nb, str) and nb in ("exact", "i8")):
+            raise ValueError("search: neighbours: 'exact' or 'i8', or the mapping {ivf: {lists, nprobe, ...}}, got %r" % (nb,))
+        elif nb == "i8" and out["k0"] + 1 > ops.KNN_JOIN_MAX_K:
+            raise ValueError("search: neighbours: i8 keeps at most %d neighbours per row (KNN_JOIN_MAX_K); k0 + 1 = %d"
+                             % (ops.KNN_JOIN_MAX_K, out["k0"] + 1))
     return out
 
 
@@ -623,6 +665,14 @@ def _search_index(p, vecs):
     if kind in ("i8", "f16"):
         return ops.DescriptorIndex(vecs, "ND", storage=kind)
     kmeans = {key: p[key] for key in ("iters", "seed") if key in p}
+    if kind == "graph":
+        entries = None
+        if p["entries"] == "medoids":
+            km = cluster.kmeans(vecs, p["lists"], **kmeans)
+            entries = graph.medoids(vecs, km.centroids, km.labels)
+        with _neighbour_index(vecs, p["neighbours"]) as nix:
+            return graph.GraphIndex.build(vecs, p["degree"], p["k0"], neighbours=nix, entries=entries,
+                                          n_entries=p.get("n_entries", 1024), seed=p.get("seed", 0))
     if kind == "ivf":
         return ivf.IVFIndex.train(vecs, p["lists"], storage=p["storage"], **kmeans)
     keep_rows = p["shortlist"] is not None and (p["refine"] is None or p["rescore"] is not None)
@@ -639,6 +689,8 @@ def _search_lists(p, index, vecs, qvecs, depth):
         return _search.search(index, vecs, qvecs, depth, p["shortlist"], exact=p["exact"])
     if kind == "ivf":
         return index.search(qvecs, depth, p["nprobe"], shortlist=p["shortlist"], exact=p["exact"])
+    if kind == "graph":
+        return index.search(qvecs, depth, beam=p["beam"], width=p["width"], seeds=p["seeds"])
     return index.search(qvecs, depth, p["nprobe"], shortlist=p["shortlist"], rescore=p["rescore"])
 
 
